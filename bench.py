@@ -11,7 +11,7 @@ The headline (``value``, ``ms_per_step``, ``roofline``) is the exact fused
 f32 scan that reads every row, SURVEY §8(d): 3 072 B per vector, 30.72 GB per
 search.  The product default for the same single query streams a resident
 int8 filter image instead and rescores its candidates exactly (bit-identical
-results); it is timed as a second leg and reported under
+results); ``--full`` times it as a second leg and reports it under
 ``accelerated_exact`` with the image's own bytes.  Batches (``--nq`` > 1,
 configs[2]) run the product path in the headline, priced over the image bytes
 (``roofline.bytes_basis``).
@@ -19,10 +19,20 @@ configs[2]) run the product path in the headline, priced over the image bytes
     python bench.py [--gpus N] [--steps K] [--warmup W] [--rows ROWS] [--d D]
                     [--k K] [--nq Q] [--metric l2|cosine|inner_product]
                     [--dtype f32|f16|qu8] [--cluster C] [--query normal|near]
-                    [--no-accelerated] [--no-cpu-baseline] [--strong-rows R]
-                    [--serve-devices 0,1,...]
+                    [--dump-outputs DIR] [--full [--no-accelerated]
+                    [--no-batch-leg] [--no-cpu-baseline] [--strong-rows R]
+                    [--serve-devices 0,1,...]]
 
-For N > 1 the line also carries ``strong`` (BASELINE's fixed 10M-row corpus
+A plain run does what the headline needs and no more: fill the corpus, W
+warmup steps, K timed steps, check the last step's result, print the line.
+``--full`` adds every other leg described here (the accelerated and configs[2]
+legs, ``strong`` and ``serve`` for N > 1, the CPU baseline); the headline
+fields mean the same in both.  ``--dump-outputs DIR`` writes what the last
+timed headline step returned, ``DIR/distances.npy`` (float32 [nq, k]) and
+``DIR/rows.npy`` (global row ids as float64 [nq, k]); the inputs are seeded,
+so two runs with the same arguments can be compared array for array.
+
+With ``--full`` and N > 1 the line also carries ``strong`` (BASELINE's fixed 10M-row corpus
 split over the N ranks) and ``serve`` (rank 0 alone: one process searching a
 row shard on every device through engine._search_all, the path a Flight
 server runs, with the RCCL all-gather and with peer copies).
@@ -74,6 +84,13 @@ def parse():
     p.add_argument("--metric", default="l2")
     p.add_argument("--dtype", default="f32", choices=["f32", "f16", "qu8"],
                    help="qu8: quint8 codes (ex/arrow/quint8), scanned by fx_knn_search_ex")
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the headline: the filter-image and "
+                        "configs[2] legs, strong scaling and the serve leg at N > 1, the CPU "
+                        "baseline (the --no-* switches below drop single legs of it)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed headline step's result to DIR/distances.npy "
+                        "(float32) and DIR/rows.npy (float64)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-verify", action="store_true",
                    help="skip the result checks and the planted rows (diagnostic builds)")
@@ -98,7 +115,12 @@ def parse():
                    help="comma-separated ordinals: also time one process searching row shards "
                         "on these devices (engine._search_all, the Flight server's path); "
                         "default at N > 1: every rank's device, from rank 0")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    if args.serve_devices and not args.full:
+        p.error("--serve-devices is a leg of --full")
+    return args
 
 
 def check_frac(name: str, frac: float) -> float:
@@ -411,7 +433,7 @@ def main():
     image = None
     image_build_ms = None
     img_bytes = None
-    want_image = not qu8 and not (single and args.no_accelerated) and \
+    want_image = not qu8 and not (single and (args.no_accelerated or not args.full)) and \
         _lib.filter_image_used(n, d, shard.dtype_id, nq, k, metric)
     if want_image:
         b0, b1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -439,7 +461,7 @@ def main():
     # 1/2/4/8 GPUs): the same exact search over strong_rows rows in total,
     # shard_rows(strong_rows, N, rank) per rank (a prefix of this rank's rows)
     strong = None
-    if world > 1 and single and args.strong_rows > 0:
+    if args.full and world > 1 and single and args.strong_rows > 0:
         s_base, s_cnt = shard_rows(args.strong_rows, world, rank)
         if s_cnt > n:
             sys.exit(f"--strong-rows {args.strong_rows} needs {s_cnt} rows per rank (> --rows)")
@@ -467,7 +489,7 @@ def main():
     # the product default for the same single query: the int8 filter image +
     # exact rescoring (bit-identical), timed as its own leg
     accel = None
-    if single and image is not None:
+    if args.full and single and image is not None:
         a_el, a_ms, res = timed_leg(make_step(shard, "search"))
         verify(res, "accelerated")
         same = bool(np.array_equal(head[1].cpu().numpy(), res[1].cpu().numpy()) and np.array_equal(
@@ -500,7 +522,7 @@ def main():
     # configs[2] beside it (BASELINE configs[2]: the same rows, a 256-query
     # cosine batch through the same resident image), one rank only
     batch = None
-    if single and image is not None and world == 1 and not args.no_batch_leg:
+    if args.full and single and image is not None and world == 1 and not args.no_batch_leg:
         batch = batch_leg(eng, shard, image, img_bytes, n, d, k, args)
 
     total_rows = n * world
@@ -557,7 +579,8 @@ def main():
     serve_devs = None
     if args.serve_devices and not qu8:
         serve_devs = [int(v) for v in args.serve_devices.split(",")]
-    elif world > 1 and single and not qu8 and torch.cuda.device_count() >= world:
+    elif args.full and world > 1 and single and not qu8 and \
+            torch.cuda.device_count() >= world:
         serve_devs = list(range(world))
     if serve_devs is not None and world > 1:
         store = dist.distributed_c10d._get_default_store()
@@ -578,13 +601,14 @@ def main():
     # N > 1 the other ranks wait on the rendezvous store (not a GPU barrier,
     # so no collective kernel of theirs spins meanwhile)
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    want_cpu = args.full and not args.no_cpu_baseline
+    if rank == 0 and want_cpu:
         try:
             cpu = cpu_baseline(args)
         finally:
             if world > 1:
                 dist.distributed_c10d._get_default_store().set("fx_bench_cpu_done", "1")
-    elif world > 1 and not args.no_cpu_baseline:
+    elif world > 1 and want_cpu:
         dist.distributed_c10d._get_default_store().wait(["fx_bench_cpu_done"],
                                                          datetime.timedelta(minutes=20))
 
@@ -644,11 +668,32 @@ def main():
             **({"configs2": batch} if batch is not None else {}),
             "cpu_baseline": cpu,
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, head[0].cpu().numpy(), head[1].cpu().numpy())
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
     return out
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path: str, dist_: np.ndarray, rows: np.ndarray) -> None:
+    """The headline's result as a caller receives it: distances.npy (float32
+    [nq, k]) and rows.npy (global row ids, float64 [nq, k]: exact below 2^53).
+    A result above DUMP_MAX_BYTES is cut to a fixed seeded sample of its
+    queries, listed in queries.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    nq, k = dist_.shape
+    cap = DUMP_MAX_BYTES // (k * 12 + 8)
+    if nq > cap:
+        pick = np.sort(np.random.default_rng(0).choice(nq, cap, replace=False))
+        dist_, rows = dist_[pick], rows[pick]
+        np.save(os.path.join(path, "queries.npy"), pick.astype(np.float64))
+    np.save(os.path.join(path, "distances.npy"), np.ascontiguousarray(dist_, dtype=np.float32))
+    np.save(os.path.join(path, "rows.npy"), np.ascontiguousarray(rows, dtype=np.float64))
 
 
 def serve_leg(eng, devs, n, d, k, metric, q, args, rank_result):

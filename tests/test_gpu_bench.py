@@ -1,6 +1,8 @@
 """bench.py keeps the driver's output contract (one JSON line with metric,
 value, roofline, cpu_baseline ...) on small shapes of each path it reports:
-the single-query scan, the batched filter, fp16 rows and quint8 codes."""
+the single-query scan, the batched filter, fp16 rows and quint8 codes.  The
+legs beside the headline run under ``--full``; a plain run times the headline
+alone and ``--dump-outputs`` writes its result."""
 
 from __future__ import annotations
 
@@ -10,6 +12,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -42,8 +45,8 @@ def run_bench(*args: str, env=None) -> dict:
     ("--dtype", "qu8"),
 ])
 def test_bench_contract(extra):
-    rec = run_bench("--rows", "300000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                    *extra)
+    rec = run_bench("--full", "--rows", "300000", "--steps", "3", "--warmup", "1",
+                    "--no-cpu-baseline", *extra)
     assert KEYS <= set(rec)
     assert rec["n_gpus"] == 1 and rec["steps"] == 3 and rec["value"] > 0
     roof = rec["roofline"]
@@ -52,9 +55,46 @@ def test_bench_contract(extra):
     assert rec["config"]["rows_per_gpu"] == 300000
 
 
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """A plain run carries the headline fields and none of --full's legs;
+    --steps sets the number of timed steps; --dump-outputs writes the last
+    step's [nq, k] result, the same arrays from run to run (seeded inputs),
+    whose first row is the planted one (row 12345 of 300000)."""
+    recs, outs = [], []
+    for steps, sub in (("3", "a"), ("1", "b")):
+        recs.append(run_bench("--rows", "300000", "--steps", steps, "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / sub)))
+        outs.append({n: np.load(tmp_path / sub / f"{n}.npy") for n in ("distances", "rows")})
+        assert sorted(os.listdir(tmp_path / sub)) == ["distances.npy", "rows.npy"]
+    for rec, steps in zip(recs, (3, 1)):
+        assert KEYS <= set(rec) and rec["steps"] == steps
+        assert rec["cpu_baseline"] is None
+        assert not {"accelerated_exact", "configs2", "strong", "serve", "filter_image"} & set(rec)
+        assert rec["ms_per_step"] > 0
+        assert rec["value"] == pytest.approx(300000 * 1e3 / rec["ms_per_step"])
+    a, b = outs
+    assert a["distances"].dtype == np.float32 and a["distances"].shape == (1, 100)
+    assert a["rows"].dtype == np.float64 and a["rows"].shape == (1, 100)
+    assert np.array_equal(a["distances"], b["distances"]) and np.array_equal(a["rows"], b["rows"])
+    assert np.all(np.diff(a["distances"][0]) >= 0)
+    # the planted row lies 1/16 from the query, every other row about sqrt(2 d) = 39 away;
+    # 1e-2 covers a float32 norm expansion (eps * 2 d = 2e-4 on the square of 1/16)
+    assert a["rows"][0, 0] == 12345 and a["distances"][0, 0] == pytest.approx(1 / 16, abs=1e-2)
+    assert len(set(a["rows"][0].tolist())) == 100 and a["rows"].min() >= 0
+    assert a["rows"].max() < 300000
+
+
+def test_bench_serve_devices_needs_full():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "100000",
+                          "--steps", "1", "--serve-devices", "0,0"],
+                         capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode != 0
+    assert "--full" in out.stderr
+
+
 def test_bench_cpu_baseline_fields():
-    rec = run_bench("--rows", "200000", "--steps", "2", "--warmup", "1", "--cpu-rows", "20000",
-                    "--cpu-seconds", "0.5")
+    rec = run_bench("--full", "--rows", "200000", "--steps", "2", "--warmup", "1",
+                    "--cpu-rows", "20000", "--cpu-seconds", "0.5")
     cpu = rec["cpu_baseline"]
     assert cpu["kind"] in ("port", "reference") and cpu["cores"] >= 1 and cpu["value"] > 0
 
@@ -68,7 +108,7 @@ def test_bench_rccl_path_one_rank():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--rows", "300000", "--steps", "3", "--warmup", "1",
+           "--gpus", "1", "--full", "--rows", "300000", "--steps", "3", "--warmup", "1",
            "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -80,7 +120,7 @@ def test_bench_rccl_path_one_rank():
 
 
 def test_bench_gpus_n_launches_n_ranks():
-    """`bench.py --gpus 2` without a launcher starts 2 ranks itself (here
+    """`bench.py --gpus 2 --full` without a launcher starts 2 ranks itself (here
     with gloo, two ranks sharing the one GPU of the box: RCCL refuses a
     duplicate device) and reports n_gpus 2 over 2 x rows, the strong-scaling
     leg (--rows in total, half per rank) and the single-process serve leg
@@ -90,9 +130,9 @@ def test_bench_gpus_n_launches_n_ranks():
     legs while rank 1 waits on the store, so the N > 1 line carries one."""
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    rec = run_bench("--gpus", "2", "--dist-backend", "gloo", "--rows", "200000", "--steps", "3",
-                    "--warmup", "1", "--cpu-rows", "20000", "--cpu-seconds", "0.5",
-                    "--serve-devices", "0,0", env=env)
+    rec = run_bench("--gpus", "2", "--full", "--dist-backend", "gloo", "--rows", "200000",
+                    "--steps", "3", "--warmup", "1", "--cpu-rows", "20000",
+                    "--cpu-seconds", "0.5", "--serve-devices", "0,0", env=env)
     assert rec["n_gpus"] == 2
     assert rec["config"]["total_rows"] == 400000
     assert rec["config"]["parallelism"].startswith(
@@ -111,8 +151,8 @@ def test_bench_gpus_n_launches_n_ranks():
 def test_bench_serve_devices_one_rank():
     """--serve-devices on a single rank (no process group): one process, three
     row shards on the one GPU, merged there."""
-    rec = run_bench("--rows", "200000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                    "--no-accelerated", "--serve-devices", "0,0,0")
+    rec = run_bench("--full", "--rows", "200000", "--steps", "2", "--warmup", "1",
+                    "--no-cpu-baseline", "--no-accelerated", "--serve-devices", "0,0,0")
     serve = rec["serve"]
     assert serve["total_rows"] == 600000 and serve["gathers"]["none"]["value"] > 0
 

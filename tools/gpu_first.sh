@@ -1,6 +1,7 @@
 #!/bin/bash
-# A quick GPU pass: box facts, the named -m gpu test files, then one default
-# bench line.  Each GPU step has its own limit; the first failure ends it.
+# A quick GPU pass: box facts, the named -m gpu test files, then one bench
+# line (pass --full for every leg beside the headline).  Each GPU step has
+# its own limit; the first failure ends it.
 #   bash tools/gpu_first.sh "tests/test_a.py tests/test_b.py" [bench args...]
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out/q

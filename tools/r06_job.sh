@@ -24,7 +24,7 @@ TESTS=${TESTS:-tests}
 K4="--dtype f16 --d 1536 --rows 6250000 --k 1000 --metric inner_product --no-batch-leg --opt i8_max_k=1024"
 for step in "$@"; do
   case $step in
-    bench) run bench 300 python -u bench.py ;;
+    bench) run bench 300 python -u bench.py --full ;;
     flightprof) run flightprof 600 python -u tools/profile_call.py --n 10000000 --d 768 --dtype f32 \
         --metric l2 --k 100 --batch 1000 --reps 30 --json gpurun_out/r06/flightprof.json ;;
     flight) run flight 600 python -u tools/bench_flight.py --n 10000000 --d 768 --k 100 --metric l2 \
@@ -36,12 +36,12 @@ for step in "$@"; do
     ksweep) run ksweep 900 python -u tools/k1000_sweep.py --queries 20 --opt i8_max_k=1024 \
         --json gpurun_out/r06/k1000_sweep.json ;;
     ktrace) run ktrace 300 rocprofv3 --kernel-trace --stats -d gpurun_out/r06/ktrace -o run \
-        --output-format csv -- python3 -u bench.py --dtype f16 --d 1536 --rows 6250000 --k 1000 \
+        --output-format csv -- python3 -u bench.py --full --dtype f16 --d 1536 --rows 6250000 --k 1000 \
         --metric inner_product --no-cpu-baseline --no-batch-leg --opt i8_max_k=1024 --steps 5 --warmup 1
       python tools/timeline.py gpurun_out/r06/ktrace/run_kernel_trace.csv qprep8 \
         > gpurun_out/r06/ktrace_timeline.txt ;;
     ctrace) run ctrace 300 rocprofv3 --kernel-trace --stats -d gpurun_out/r06/ctrace -o run \
-        --output-format csv -- python3 -u bench.py --no-cpu-baseline --no-batch-leg --steps 5 --warmup 1
+        --output-format csv -- python3 -u bench.py --full --no-cpu-baseline --no-batch-leg --steps 5 --warmup 1
       python tools/timeline.py gpurun_out/r06/ctrace/run_kernel_trace.csv qprep8 \
         > gpurun_out/r06/ctrace_timeline.txt ;;
     flightr) run flightr 600 python -u tools/bench_flight.py --n 10000000 --d 768 --k 100 --metric l2 \
@@ -102,9 +102,9 @@ for step in "$@"; do
         "--no-batch-leg --opt i8_sample_ratio=5" "--no-batch-leg --opt i8_sample_ratio=7" \
         "$K4" "$K4 --opt i8_sample_ratio=6" ;;
     flight0) run flight0 300 python -u tools/bench_flight.py --n 100000 --d 128 --k 10 --metric l2 --reps 60 ;;
-    k1000) run k1000a 300 python -u bench.py --dtype f16 --d 1536 --rows 6250000 --k 1000 \
+    k1000) run k1000a 300 python -u bench.py --full --dtype f16 --d 1536 --rows 6250000 --k 1000 \
         --metric inner_product --no-cpu-baseline --no-batch-leg --opt i8_max_k=1024
-      run k1000b 300 python -u bench.py --dtype f16 --d 1536 --rows 6250000 --k 1000 \
+      run k1000b 300 python -u bench.py --full --dtype f16 --d 1536 --rows 6250000 --k 1000 \
         --metric inner_product --no-cpu-baseline --no-batch-leg --opt i8_max_k=1024 --query near ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac

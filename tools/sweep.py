@@ -6,7 +6,8 @@
 Each quoted ARGS is one bench.py configuration (leading NAME=VALUE tokens are
 environment variables for that run, e.g. "FX_FILTER_DIAG=2 --nq 256" with
 ``--libs diag`` for the diagnostic build's switches); every (rep, config, lib) runs
-bench.py in its own process under a time limit (``--no-cpu-baseline`` added),
+bench.py in its own process under a time limit (``--full --no-cpu-baseline``
+added: the headline and the filter-image legs beside it),
 and one line per run is printed and appended to ``--out``.  A library NAME
 other than ``new`` is ``fenix_amd/lib/libfenix_knn_NAME.so`` (loaded through
 FENIX_AMD_LIB; build it first, e.g. ``make -C fenix_amd/csrc
@@ -62,7 +63,7 @@ def main() -> int:
                     env[key] = val
                 cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, "-u",
                        os.path.join(ROOT, "bench.py"), *toks, "--steps",
-                       str(a.steps), "--warmup", str(a.warmup), "--no-cpu-baseline"]
+                       str(a.steps), "--warmup", str(a.warmup), "--full", "--no-cpu-baseline"]
                 r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, env=env)
                 if r.returncode != 0:
                     print(f"FAILED rc={r.returncode} lib={lib} args={cfg}\n{r.stderr[-3000:]}",
