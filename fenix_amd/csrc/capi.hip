@@ -42,9 +42,9 @@ static const char* const kOptNames[kOptCount] = {
     "batched", "batch_min_queries", "batch_cap", "batch_sample_ratio",
     "force_fallback", "scan_interleave", "q8_dma", "filter_image", "batch_ub_test",
     "single_query_image", "i8_max_k", "img6", "img8", "i8_sample_ratio", "i8_grow_ratio",
-    "select_prune"};
+    "select_prune", "scan_stream"};
 static std::atomic<int64_t> g_opts[kOptCount] = {{1}, {2}, {0}, {0}, {0}, {-1}, {1}, {8}, {1}, {1},
-                                                 {1024}, {1}, {1}, {8}, {16}, {1}};
+                                                 {1024}, {1}, {1}, {8}, {16}, {1}, {-1}};
 
 int64_t option(Option o) { return g_opts[o].load(std::memory_order_relaxed); }
 

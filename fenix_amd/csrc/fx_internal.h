@@ -34,6 +34,7 @@ enum Option : int {
   kOptI8SampleRatio,  // int8 images: F1 holds every r1-th tile (filter_phases_i8)
   kOptI8GrowRatio,    // int8 images: the samples before F1 shrink by r2 each
   kOptSelectPrune,    // int8 images: 1: selects at k >= 512 prune first; 2: any k; 0: never
+  kOptScanStream,     // plain f32 / f16 scans: 1: streaming kernel, 0: register tiles, -1: by class
   kOptCount
 };
 int64_t option(Option o);
@@ -89,6 +90,10 @@ struct ScanPlan {
   // list); null when not applicable.  Same rows_per_block (its U divides it).
   ScanKernelFn fn_dma;
   size_t smem_dma;
+  // f32 / f16 rows of exactly 16 L slots streamed through a register ring
+  // (plain scans: no mask, no row list); null when not applicable or switched
+  // off.  Same LDS, grid and rows_per_block as fn.
+  ScanKernelFn fn_stream;
 };
 
 int plan_scan(int64_t n, int64_t d, int dtype, int64_t k, int metric, bool aligned, ScanPlan* p);

@@ -119,6 +119,19 @@ __device__ __forceinline__ V load_stream(const V* p) {
 #endif
 }
 
+// the same through a pointer known to be global memory (a global_load whose
+// completion the compiler counts in order, where a flat load is not)
+template <typename V>
+__device__ __forceinline__ V load_global_stream(const V* p) {
+  typedef const V __attribute__((address_space(1))) GV;
+  GV* g = (GV*)p;
+#if FX_NONTEMPORAL
+  return __builtin_nontemporal_load(g);
+#else
+  return *g;
+#endif
+}
+
 // k-th smallest (1-indexed) composite among buf[0..cnt), cnt >= k >= 1.
 // Also returns how many entries equal to the k-th belong to the k smallest
 // (only the empty sentinel can repeat: real composites carry unique rows).
@@ -226,10 +239,11 @@ __device__ int wave_compact(uint64_t* buf, int cnt, uint64_t T, int quota_eq, in
 // L: slots per lane per row pass (the row covers 16*L slots per pass, more
 // passes if the row is longer); U: rows per lane group per tile.
 //
-// Software pipeline: while a wave reduces tile i it already has tile i+1's
-// loads in flight (two register tiles, the loop unrolled by two so no moves),
-// so every wave keeps HBM requests outstanding continuously instead of
-// alternating load bursts with compute.
+// Software pipeline: tile i+1's loads are issued before tile i is reduced
+// (two register tiles, the loop unrolled by two so no moves).  Each load sits
+// under its own predicate, so the compiler drains the queue (vmcnt(0)) before
+// the first sum: the waves of a CU cover each other's bubbles, a wave does not
+// overlap its own.  stream_scan_kernel below is the form that does.
 
 template <typename T, int W, int L, int U>
 struct RowTile {
@@ -279,6 +293,26 @@ __device__ __forceinline__ void tile_load(RowTile<T, W, L, U>& t, int64_t it, in
       } else {
         t.v[u][cc] = V(0);
       }
+    }
+  }
+}
+
+// One 16-B slot of one f32 / f16 row against the matching query elements, in
+// ascending element order (every path sums a row in the same order).
+template <int W, int METRIC, typename V>
+__device__ __forceinline__ void slot_accumulate(const V& v, const float (&qv)[W], float& acc,
+                                                float& acc2) {
+#pragma unroll
+  for (int e = 0; e < W; ++e) {
+    const float x = elem<W>(v, e);
+    if constexpr (METRIC == 0) {
+      const float d = x - qv[e];
+      acc = fmaf(d, d, acc);
+    } else if constexpr (METRIC == 1) {
+      acc = fmaf(x, qv[e], acc);
+    } else {
+      acc = fmaf(x, qv[e], acc);
+      acc2 = fmaf(x, x, acc2);
     }
   }
 }
@@ -352,21 +386,7 @@ __device__ __forceinline__ void tile_accumulate(const RowTile<T, W, L, U>& t, in
 #pragma unroll
     for (int e = 0; e < W; ++e) qv[e] = c.q_lds[s * W + e];
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-#pragma unroll
-      for (int e = 0; e < W; ++e) {
-        const float x = elem<W>(t.v[u][cc], e);
-        if constexpr (METRIC == 0) {
-          const float d = x - qv[e];
-          acc[u] = fmaf(d, d, acc[u]);
-        } else if constexpr (METRIC == 1) {
-          acc[u] = fmaf(x, qv[e], acc[u]);
-        } else {
-          acc[u] = fmaf(x, qv[e], acc[u]);
-          acc2[u] = fmaf(x, x, acc2[u]);
-        }
-      }
-    }
+    for (int u = 0; u < U; ++u) slot_accumulate<W, METRIC>(t.v[u][cc], qv, acc[u], acc2[u]);
   }
 }
 
@@ -443,20 +463,16 @@ __device__ __forceinline__ void tile_consume(const RowTile<T, W, L, U>& t, const
 template <typename T>
 constexpr int kMinWaves = sizeof(T) == 1 ? FX_Q8_WAVES : 1;
 
-template <typename T, int W, int L, int U, int METRIC, bool PIPE, bool DMA = false>
-__global__ void __launch_bounds__(256, kMinWaves<T>) scan_kernel(ScanArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-
+// Query -> LDS (padded to qfl floats) and the per-lane context.  False: this
+// workgroup's query is gated out and the whole workgroup returns.
+template <typename T, int W, int METRIC>
+__device__ __forceinline__ bool scan_begin(const ScanArgs& a, unsigned char* smem, int qfl,
+                                           ScanCtx& c) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int S = a.d / W;
-  constexpr int CH = 16 * L;
-  const int nch = (S + CH - 1) / CH;
-  const int qfl = nch * CH * W;  // padded query floats
-
   float* q_lds = reinterpret_cast<float*>(smem);
   const int qi = blockIdx.y;
   // the batched path's overflow fallback: only queries whose count overflowed
-  if (a.gate != nullptr && (int64_t)a.gate[(size_t)qi * kCountStride] <= a.gate_cap) return;
+  if (a.gate != nullptr && (int64_t)a.gate[(size_t)qi * kCountStride] <= a.gate_cap) return false;
   const float* qg = a.q + (size_t)qi * a.d;
   for (int i = threadIdx.x; i < qfl; i += 256) {
     float v = i < a.d ? qg[i] : 0.f;
@@ -467,12 +483,11 @@ __global__ void __launch_bounds__(256, kMinWaves<T>) scan_kernel(ScanArgs a) {
   }
   __syncthreads();
 
-  ScanCtx c;
   c.a = &a;
   c.q_lds = q_lds;
   c.buf = reinterpret_cast<uint64_t*>(smem + a.qbytes) + (size_t)wid * a.cap;
   c.hist = reinterpret_cast<uint32_t*>(smem + a.qbytes + (size_t)4 * a.cap * 8) + wid * 256;
-  c.S = S;
+  c.S = a.d / W;
   c.lane = lane;
   c.grp = lane >> 4;
   c.jl = lane & 15;
@@ -490,14 +505,18 @@ __global__ void __launch_bounds__(256, kMinWaves<T>) scan_kernel(ScanArgs a) {
     for (int m = 32; m >= 1; m >>= 1) s2 += __shfl_xor(s2, m);
     c.qnorm = fmaxf(sqrtf(s2), 1e-12f);
   }
+  return true;
+}
 
-  // A block step is 16U rows (4U per wave).  Contiguous: block b owns one
-  // range of rows_per_block.  Interleaved: block steps are dealt round-robin
-  // over the grid, so at any time the whole chip reads one window of the
-  // corpus (DRAM pages stay open across CUs: tools/hbm_sweep.hip).  Either
-  // partition gives the same result (the merge orders by (distance, row)).
+// A block step is 16U rows (4U per wave).  Contiguous: block b owns one
+// range of rows_per_block.  Interleaved: block steps are dealt round-robin
+// over the grid, so at any time the whole chip reads one window of the
+// corpus (DRAM pages stay open across CUs: tools/hbm_sweep.hip).  Either
+// partition gives the same result (the merge orders by (distance, row)).
+template <int U>
+__device__ __forceinline__ void scan_partition(const ScanArgs& a, ScanCtx& c, int64_t& lo,
+                                               int64_t& gstep) {
   const int64_t step = 16 * U;
-  int64_t lo, gstep;
   if (a.interleave & 1) {
     lo = (int64_t)blockIdx.x * step;
     c.hi = a.n;
@@ -507,6 +526,181 @@ __global__ void __launch_bounds__(256, kMinWaves<T>) scan_kernel(ScanArgs a) {
     c.hi = lo + a.rows_per_block < a.n ? lo + a.rows_per_block : a.n;
     gstep = step;
   }
+}
+
+// Each wave's list -> its k best; the block's 4 lists -> one list of k in
+// out_lists (a quarter of the candidates for the merge kernels).
+__device__ __forceinline__ void scan_end(const ScanArgs& a, unsigned char* smem, const ScanCtx& c,
+                                         int cnt) {
+  const int lane = c.lane, wid = threadIdx.x >> 6, qi = c.qi;
+  if (!c.topk) return;
+  wave_sync();
+  if (cnt > a.k) {
+    int quota;
+    const uint64_t kth = wave_select(c.buf, cnt, a.k, c.hist, lane, &quota);
+    cnt = wave_compact(c.buf, cnt, kth, quota, lane);
+  }
+  // Fold the block's 4 wave lists (k each, padded) into one list of k:
+  // a quarter of the candidates for the merge kernels (block-wide select).
+  constexpr int kMaxPerLane = 16;  // k <= 1024
+  uint64_t mine[kMaxPerLane];
+#pragma unroll
+  for (int j = 0; j < kMaxPerLane; ++j) {
+    const int i = lane + j * kWave;
+    mine[j] = i < cnt ? c.buf[i] : kEmpty;
+  }
+  __syncthreads();
+  uint64_t* all = reinterpret_cast<uint64_t*>(smem + a.qbytes);  // 4k entries fit in 4 caps
+  uint64_t v_or = 0, v_and = ~0ull;
+#pragma unroll
+  for (int j = 0; j < kMaxPerLane; ++j) {
+    const int i = lane + j * kWave;
+    if (i < a.k) {
+      all[wid * a.k + i] = mine[j];
+      v_or |= mine[j];
+      v_and &= mine[j];
+    }
+  }
+  MergeShared* ms = reinterpret_cast<MergeShared*>(smem + a.qbytes + (size_t)4 * a.cap * 8);
+  block_reset(ms);
+  __syncthreads();
+  block_or_and(v_or, v_and, ms);
+  __syncthreads();
+  const size_t ls = a.list_stride > 0 ? (size_t)a.list_stride : (size_t)gridDim.x;
+  uint64_t* out = a.out_lists + ((size_t)qi * ls + a.list_base + blockIdx.x) * (size_t)a.k;
+  block_keep_k<256>(all, 4 * a.k, a.k, out, ms);
+}
+
+// 16-B registers per lane of the streaming kernel's load ring (one less is
+// in flight while a slot is summed).  10M x 768 f32, one block per CU, against
+// the register tiles' 4.361 ms: 6 -> 4.278, 8 -> 4.303, 12 -> 4.348; issuing
+// after the sums instead, into the register just read: 6 -> 4.317, 8 -> 4.332
+// (profiles/stream_ring_ab.log).
+#ifndef FX_SCAN_RING
+#define FX_SCAN_RING 6
+#endif
+// ring depth for a tile of U * L loads: the largest divisor of it <= FX_SCAN_RING
+template <int L, int U>
+constexpr int ring_depth() {
+  int r = FX_SCAN_RING < U * L ? FX_SCAN_RING : U * L;
+  while ((U * L) % r != 0) --r;
+  return r;
+}
+
+// One tile of the streaming kernel: the lane's U * L loads (row u, slot cc at
+// stream position u * L + cc) pass through `ring`; position j is consumed from
+// ring[j % R] once position j + R - 1 has been issued into the register that
+// position j - 1 left, from this tile's rows or the next tile's (cur, nxt: the lane's first slot of each row,
+// as a slot index from X; nothing is issued on the wave's LAST tile).
+template <typename T, int W, int L, int U, int METRIC, int R, bool QREG, bool LAST>
+__device__ __forceinline__ void ring_tile(typename VecT<T, W>::type (&ring)[R],
+                                          const typename VecT<T, W>::type* X,
+                                          const int64_t (&cur)[U], const int64_t (&nxt)[U],
+                                          const float (&qreg)[QREG ? L : 1][W], int64_t it,
+                                          const ScanCtx& c, uint64_t& thr, int& cnt) {
+  RowTile<T, W, 1, U> t;  // rows only: the data is in the ring
+  float acc[U], acc2[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    t.row[u] = it + u * 4 + c.grp;
+    t.valid[u] = t.row[u] < c.hi;
+    t.src[u] = t.row[u];
+    acc[u] = acc2[u] = 0.f;
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+#pragma unroll
+    for (int cc = 0; cc < L; ++cc) {
+      // issue before the sums: position j - 1's register is free, and the next
+      // request does not wait for this slot's arithmetic
+      const int j = u * L + cc, jn = j + R - 1;
+      if (jn < U * L) {
+        ring[jn % R] = load_global_stream(X + cur[jn / L] + (jn % L) * 16);
+      } else if constexpr (!LAST) {
+        ring[jn % R] = load_global_stream(X + nxt[(jn - U * L) / L] + ((jn - U * L) % L) * 16);
+      }
+      if constexpr (QREG) {
+        slot_accumulate<W, METRIC>(ring[j % R], qreg[cc], acc[u], acc2[u]);
+      } else {
+        float qv[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) qv[e] = c.q_lds[(cc * 16 + c.jl) * W + e];
+        slot_accumulate<W, METRIC>(ring[j % R], qv, acc[u], acc2[u]);
+      }
+    }
+  }
+  tile_finish<T, W, 1, U, METRIC>(t, acc, acc2, c, thr, cnt);
+}
+
+// Streaming kernel for plain scans (no mask, no row list) of f32 / f16 rows of
+// exactly 16 * L slots: every load is unconditional, so the compiler counts
+// its waits (none drains the queue in the main loop) and a wave always has
+// R - 1 or more loads in flight while it reduces the oldest.  Rows past the range are clamped to
+// its last row (read again, never past it) and dropped by tile_finish's
+// `valid`.  Same row-to-lane mapping, block steps and per-row arithmetic as
+// scan_kernel: the distances are bit-identical.
+template <typename T, int W, int L, int U, int METRIC>
+__global__ void __launch_bounds__(256, 2) stream_scan_kernel(ScanArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  using V = typename VecT<T, W>::type;
+  constexpr int R = ring_depth<L, U>();
+  constexpr bool QREG = L * W <= 48;  // the lane's query slots fit in registers
+  ScanCtx c;
+  if (!scan_begin<T, W, METRIC>(a, smem, 16 * L * W, c)) return;
+  int64_t lo, gstep;
+  scan_partition<U>(a, c, lo, gstep);
+  uint64_t thr = kEmpty;
+  int cnt = 0;
+  const int wid = threadIdx.x >> 6;
+  const int64_t first = lo + (int64_t)wid * 4 * U;
+  const int64_t ntile = first < c.hi ? (c.hi - first + gstep - 1) / gstep : 0;
+  if (ntile > 0) {
+    float qreg[QREG ? L : 1][W];
+    if constexpr (QREG) {
+#pragma unroll
+      for (int cc = 0; cc < L; ++cc)
+#pragma unroll
+        for (int e = 0; e < W; ++e) qreg[cc][e] = c.q_lds[(cc * 16 + c.jl) * W + e];
+    }
+    const V* X = reinterpret_cast<const V*>(a.X);
+    const int64_t last = c.hi - 1;
+    int64_t cur[U], nxt[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t row = first + u * 4 + c.grp;
+      cur[u] = (row < last ? row : last) * (16 * L) + c.jl;
+    }
+    V ring[R];
+#pragma unroll
+    for (int j = 0; j < R - 1; ++j) ring[j] = load_global_stream(X + cur[j / L] + (j % L) * 16);
+    int64_t it = first;
+    for (int64_t i = 1; i < ntile; ++i, it += gstep) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t row = it + gstep + u * 4 + c.grp;
+        nxt[u] = (row < last ? row : last) * (16 * L) + c.jl;
+      }
+      ring_tile<T, W, L, U, METRIC, R, QREG, false>(ring, X, cur, nxt, qreg, it, c, thr, cnt);
+#pragma unroll
+      for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+    }
+    ring_tile<T, W, L, U, METRIC, R, QREG, true>(ring, X, cur, cur, qreg, it, c, thr, cnt);
+  }
+  scan_end(a, smem, c, cnt);
+}
+
+template <typename T, int W, int L, int U, int METRIC, bool PIPE, bool DMA = false>
+__global__ void __launch_bounds__(256, kMinWaves<T>) scan_kernel(ScanArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int S = a.d / W;
+  constexpr int CH = 16 * L;
+  const int nch = (S + CH - 1) / CH;
+  ScanCtx c;
+  if (!scan_begin<T, W, METRIC>(a, smem, nch * CH * W, c)) return;
+  int64_t lo, gstep;
+  scan_partition<U>(a, c, lo, gstep);
 
   uint64_t thr = kEmpty;
   int cnt = 0;
@@ -644,42 +838,7 @@ __global__ void __launch_bounds__(256, kMinWaves<T>) scan_kernel(ScanArgs a) {
     }
   }
 
-  if (!c.topk) return;
-  wave_sync();
-  if (cnt > a.k) {
-    int quota;
-    const uint64_t kth = wave_select(c.buf, cnt, a.k, c.hist, lane, &quota);
-    cnt = wave_compact(c.buf, cnt, kth, quota, lane);
-  }
-  // Fold the block's 4 wave lists (k each, padded) into one list of k:
-  // a quarter of the candidates for the merge kernels (block-wide select).
-  constexpr int kMaxPerLane = 16;  // k <= 1024
-  uint64_t mine[kMaxPerLane];
-#pragma unroll
-  for (int j = 0; j < kMaxPerLane; ++j) {
-    const int i = lane + j * kWave;
-    mine[j] = i < cnt ? c.buf[i] : kEmpty;
-  }
-  __syncthreads();
-  uint64_t* all = reinterpret_cast<uint64_t*>(smem + a.qbytes);  // 4k entries fit in 4 caps
-  uint64_t v_or = 0, v_and = ~0ull;
-#pragma unroll
-  for (int j = 0; j < kMaxPerLane; ++j) {
-    const int i = lane + j * kWave;
-    if (i < a.k) {
-      all[wid * a.k + i] = mine[j];
-      v_or |= mine[j];
-      v_and &= mine[j];
-    }
-  }
-  MergeShared* ms = reinterpret_cast<MergeShared*>(smem + a.qbytes + (size_t)4 * a.cap * 8);
-  block_reset(ms);
-  __syncthreads();
-  block_or_and(v_or, v_and, ms);
-  __syncthreads();
-  const size_t ls = a.list_stride > 0 ? (size_t)a.list_stride : (size_t)gridDim.x;
-  uint64_t* out = a.out_lists + ((size_t)qi * ls + a.list_base + blockIdx.x) * (size_t)a.k;
-  block_keep_k<256>(all, 4 * a.k, a.k, out, ms);
+  scan_end(a, smem, c, cnt);
 }
 
 // ----------------------------------------------------- dispatch / planning --
@@ -722,6 +881,39 @@ static ScanKernelFn pick_l(int L) {
       default: return scan_kernel<T, W, 24, 1, METRIC, kPipe<T, 24>>;
     }
   }
+}
+
+template <typename T, int W, int METRIC>
+static ScanKernelFn pick_stream_l(int L) {
+  switch (L) {
+    case 1: return stream_scan_kernel<T, W, 1, FX_U1, METRIC>;
+    case 2: return stream_scan_kernel<T, W, 2, FX_U2, METRIC>;
+    case 3: return stream_scan_kernel<T, W, 3, FX_U3, METRIC>;
+    case 4: return stream_scan_kernel<T, W, 4, FX_U4, METRIC>;
+    case 6: return stream_scan_kernel<T, W, 6, FX_U6, METRIC>;
+    case 8: return stream_scan_kernel<T, W, 8, FX_U8, METRIC>;
+    case 12: return stream_scan_kernel<T, W, 12, FX_U12, METRIC>;
+    case 16: return stream_scan_kernel<T, W, 16, 1, METRIC>;
+    default: return stream_scan_kernel<T, W, 24, 1, METRIC>;
+  }
+}
+
+// the streaming kernel for vector-width f32 / f16 rows of exactly 16 * L slots
+static ScanKernelFn select_stream_kernel(int dtype, int metric, int L) {
+  if (dtype == FX_DTYPE_F32) {
+    if (metric == 0) return pick_stream_l<float, 4, 0>(L);
+    if (metric == 1) return pick_stream_l<float, 4, 1>(L);
+    return pick_stream_l<float, 4, 2>(L);
+  }
+  if (metric == 0) return pick_stream_l<_Float16, 8, 0>(L);
+  if (metric == 1) return pick_stream_l<_Float16, 8, 1>(L);
+  return pick_stream_l<_Float16, 8, 2>(L);
+}
+
+// Classes (dtype, L) whose plain scans stream by default ("scan_stream" -1):
+// those measured faster than the register tiles.
+static bool stream_default(int dtype, int L) {
+  return dtype == FX_DTYPE_F32 && L == 12;
 }
 
 template <typename T, int METRIC>
@@ -846,6 +1038,14 @@ int plan_scan(int64_t n, int64_t d, int dtype, int64_t k, int metric, bool align
       p->smem_dma = sd;
     }
   }
+  // Plain scans of f32 / f16 rows that fill their 16 * L slots exactly go
+  // through the streaming kernel where stream_default says so; the
+  // "scan_stream" option (test switch) overrides.  Same LDS, same grid.
+  p->fn_stream = nullptr;
+  if (dtype != FX_DTYPE_QU8 && W > 1 && S == CH) {
+    const int64_t o = option(kOptScanStream);
+    if (o < 0 ? stream_default(dtype, L) : o != 0) p->fn_stream = select_stream_kernel(dtype, metric, L);
+  }
   p->W = W;
   p->L = L;
   p->U = U;
@@ -855,7 +1055,9 @@ int plan_scan(int64_t n, int64_t d, int dtype, int64_t k, int metric, bool align
   int cus = 0, occ = 0;
   int rc = device_cus(&cus);
   if (rc) return rc;
-  rc = kernel_occupancy((const void*)p->fn, 256, smem, &occ);
+  // (the streaming kernel needs fewer registers than the tiles: its own limit)
+  rc = kernel_occupancy((const void*)(p->fn_stream != nullptr ? p->fn_stream : p->fn), 256, smem,
+                        &occ);
   if (rc) return rc;
   if (p->fn_dma != nullptr) {  // one grid serves both variants: the smaller occupancy
     int occ2 = 0;
@@ -930,13 +1132,15 @@ int launch_scan(const ScanPlan& p, const ScanArgs& a, int64_t nq, hipStream_t st
     hipLaunchKernelGGL(p.fn_dma, grid, dim3(256), p.smem_dma, stream, b);
     return check_launch("scan_kernel (quint8 LDS-DMA)");
   }
+  const bool stream_fn = p.fn_stream != nullptr && a.mask == nullptr && a.rows == nullptr;
+  const ScanKernelFn fn = stream_fn ? p.fn_stream : p.fn;
   if (p.smem > 64 * 1024) {
-    if (int rc = allow_lds((const void*)p.fn)) return rc;
+    if (int rc = allow_lds((const void*)fn)) return rc;
   }
   ScanArgs b = a;
   b.interleave = p.interleave;
-  hipLaunchKernelGGL(p.fn, grid, dim3(256), p.smem, stream, b);
-  return check_launch("scan_kernel");
+  hipLaunchKernelGGL(fn, grid, dim3(256), p.smem, stream, b);
+  return check_launch(stream_fn ? "stream_scan_kernel" : "scan_kernel");
 }
 
 }  // namespace fx

@@ -111,6 +111,9 @@ int fx_device_count(int* out);
  *   "scan_interleave"    -1  -1: by row size; 0: one row range per workgroup;
  *                            1: block steps dealt round-robin over the grid
  *   "q8_dma"              1  0: quint8 scans without the LDS-DMA ring
+ *   "scan_stream"        -1  plain f32 / f16 scans of rows that fill their slots:
+ *                            1: streaming kernel (register ring, counted waits);
+ *                            0: register tiles; -1: by (dtype, row length) class
  * fx_set_option: FX_EINVAL for an unknown name.  Options are read when a call
  * plans its launches; set them while no search is in flight.
  */

@@ -5,10 +5,13 @@
 // default policy, register loads vs LDS-DMA (global_load_lds_dwordx4).
 //
 //   hipcc -O3 --offload-arch=gfx950 -o /tmp/hbm_sweep tools/hbm_sweep.hip && /tmp/hbm_sweep [GB]
+// HBM_SWEEP_ROWS=1: the scan's row patterns only; HBM_SWEEP_RING=1: its rolling-window variants.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+
+#include <type_traits>
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -117,6 +120,66 @@ __global__ void __launch_bounds__(256) k_rows(const u32x4* __restrict__ p, int64
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int c = 0; c < 12; ++c) acc ^= v[u][c][0] ^ v[u][c][1] ^ v[u][c][2] ^ v[u][c][3];
+  }
+  if (acc == 0x12345678u) out[blockIdx.x] = acc;
+}
+
+// the scan's pattern as a rolling window: the lane's 12U loads of a block step
+// pass through a ring of R registers (consume the oldest, issue the next into
+// the same register: counted vmcnt(R-1) waits, R loads in flight all the
+// time); loads are unconditional, rows past the end clamped to the last row.
+// COL: stream order slot-major (for c, for u) instead of row-major.
+// WI: a step's rows dealt to the waves 4 at a time (row = r0 + u*16 + wid*4 + g),
+// so the four waves of a workgroup request adjacent rows at the same moment.
+template <int U, int R, bool COL, bool WI>
+__global__ void __launch_bounds__(256) k_rows_ring(const u32x4* __restrict__ p, int64_t n16,
+                                                   uint32_t* __restrict__ out) {
+  constexpr int S = 192, N = 12 * U;
+  static_assert(N % R == 0, "the ring depth divides a step's loads");
+  typedef const u32x4 __attribute__((address_space(1))) G;
+  G* gp = (G*)p;
+  const int64_t rows = n16 / S, last = rows - 1;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, g = lane >> 4, j = lane & 15;
+  const int64_t gstep = (int64_t)gridDim.x * 16 * U;
+  const int64_t first = (int64_t)blockIdx.x * 16 * U + (WI ? wid * 4 : wid * 4 * U) + g;
+  const int64_t ntile = first - g < rows ? (rows - (first - g) + gstep - 1) / gstep : 0;
+  uint32_t acc = 0;
+  if (ntile > 0) {
+    int64_t cur[U], nxt[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t row = first + u * (WI ? 16 : 4);
+      cur[u] = (row < last ? row : last) * S + j;
+    }
+    u32x4 ring[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+      ring[i] = __builtin_nontemporal_load(gp + cur[COL ? i % U : i / 12] + (COL ? i / U : i % 12) * 16);
+    // one block step; nothing is issued for the step after the last
+    auto step = [&](auto is_last) {
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        asm volatile("" ::"v"(ring[i % R]));  // the oldest load is consumed here, not later
+        const u32x4 v = ring[i % R];
+        acc ^= v[0] ^ v[1] ^ v[2] ^ v[3];
+        const int in = i + R, im = in % N;
+        const int64_t base = in < N ? cur[COL ? im % U : im / 12] : nxt[COL ? im % U : im / 12];
+        if (in < N || !decltype(is_last)::value)
+          ring[i % R] = __builtin_nontemporal_load(gp + base + (COL ? im / U : im % 12) * 16);
+        __builtin_amdgcn_sched_barrier(0);  // keep consume -> issue order: exactly R in flight
+      }
+    };
+    for (int64_t t = 1; t < ntile; ++t) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t row = first + t * gstep + u * (WI ? 16 : 4);
+        nxt[u] = (row < last ? row : last) * S + j;
+      }
+      step(std::false_type());
+#pragma unroll
+      for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+    }
+    step(std::true_type());
   }
   if (acc == 0x12345678u) out[blockIdx.x] = acc;
 }
@@ -263,6 +326,20 @@ static double run(const char* name, void (*fn)(const void*, int64_t, uint32_t*, 
   static void NAME(const void* p, int64_t n16, uint32_t* out, int blocks, hipStream_t s) { \
     hipLaunchKernelGGL((k_tile<KB>), dim3(blocks), dim3(512), 0, s, (const u32x4*)p, n16, out); \
   }
+#define RING(NAME, R, COL, WI)                                                              \
+  static void NAME(const void* p, int64_t n16, uint32_t* out, int blocks, hipStream_t s) { \
+    hipLaunchKernelGGL((k_rows_ring<2, R, COL, WI>), dim3(blocks), dim3(256), 0, s,         \
+                       (const u32x4*)p, n16, out);                                          \
+  }
+RING(ring_4, 4, false, false)
+RING(ring_6, 6, false, false)
+RING(ring_8, 8, false, false)
+RING(ring_12, 12, false, false)
+RING(ring_24, 24, false, false)
+RING(ring_8_col, 8, true, false)
+RING(ring_12_col, 12, true, false)
+RING(ring_8_wi, 8, false, true)
+RING(ring_12_wi, 12, false, true)
 TILE(tile_128, 128)
 TILE(tile_256, 256)
 TILE(tile_512, 512)
@@ -315,15 +392,30 @@ int main(int argc, char** argv) {
       {"stride T512 U4 nt", stride_512_4_nt, 512},   {"stride T512 U8 nt", stride_512_8_nt, 512},
       {"stride T256 U8 plain", stride_256_8_pl, 256}, {"wave T256 U12 nt", wave_256_12_nt, 256},
   };
+  // HBM_SWEEP_RING: the rolling-window variants of the scan's pattern at 1 and
+  // 2 workgroups per CU, with the tile pattern and the ceiling line beside them
+  const bool ring_only = getenv("HBM_SWEEP_RING") != nullptr;
+  V gv[] = {
+      {"rows ring R4", ring_4, 256},          {"rows ring R6", ring_6, 256},
+      {"rows ring R8", ring_8, 256},          {"rows ring R12", ring_12, 256},
+      {"rows ring R24", ring_24, 256},        {"rows ring R8 slot-major", ring_8_col, 256},
+      {"rows ring R12 slot-major", ring_12_col, 256},
+      {"rows ring R8 wave-interleaved", ring_8_wi, 256},
+      {"rows ring R12 wave-interleaved", ring_12_wi, 256},
+      {"rows (scan pattern) U2", rows_2, 256}, {"stride T256 U8 nt", stride_256_8_nt, 256},
+  };
   double best = 0;
   const char* bestn = "";
   int bestb = 0;
-  const V* list = rows_only ? rv : vs;
-  const int nlist = rows_only ? (int)(sizeof(rv) / sizeof(rv[0])) : (int)(sizeof(vs) / sizeof(vs[0]));
+  const V* list = ring_only ? gv : rows_only ? rv : vs;
+  const int nlist = ring_only   ? (int)(sizeof(gv) / sizeof(gv[0]))
+                    : rows_only ? (int)(sizeof(rv) / sizeof(rv[0]))
+                                : (int)(sizeof(vs) / sizeof(vs[0]));
   for (int vi = 0; vi < nlist; ++vi) {
     const V& v = list[vi];
     for (int eighths : {4, 8, 12, 16, 24, 32}) {
       if (v.threads * eighths > 2048 * 8) continue;
+      if (ring_only && eighths != 8 && eighths != 16) continue;
       const double t = run(v.name, v.fn, p, n16, out, cus * eighths / 8, reps);
       if (t > best) {
         best = t;
