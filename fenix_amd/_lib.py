@@ -427,10 +427,13 @@ BUILD_INFO = os.path.join(HERE, "lib", "build_info.json")
 
 def sources_sha() -> str:
     """SHA-256 (16 hex digits) over the library's sources (csrc/*.hip, *.h,
-    the Makefile and include/*.h, by name and content, sorted)."""
+    csrc/filter/*.inc, the Makefile and include/*.h, by name and content,
+    sorted)."""
     h = hashlib.sha256()
     files = [os.path.join(CSRC, f) for f in os.listdir(CSRC)
              if f.endswith((".hip", ".h")) or f == "Makefile"]
+    files += [os.path.join(CSRC, "filter", f) for f in os.listdir(os.path.join(CSRC, "filter"))
+              if f.endswith(".inc")]
     files += [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.endswith(".h")]
     for p in sorted(files):
         h.update(os.path.relpath(p, os.path.dirname(HERE)).encode() + b"\0")

@@ -208,7 +208,7 @@ struct BatchLayout {
       off_topd, off_topr, off_prune, total;
 };
 
-// The fp16-MFMA filter (knn_filter.hip).  Diagnostic builds keep the
+// The fp16-MFMA filter (knn_filter.hip, kernels in filter/*.inc).  Diagnostic builds keep the
 // rejected fp32-MFMA batch kernel (knn_batch.hip) behind FX_BATCH_FILTER=0.
 static bool use_filter() { return diag_env("FX_BATCH_FILTER", 1) != 0; }
 
@@ -534,7 +534,7 @@ static int fallback_search(const SearchLayout& s, const void* corpus, int dtype,
 // stream the image (half the bytes) and the rescoring reads the f32 rows.
 //
 // An int8 filter image (fx_filter_image8) gives bounds ~30x wider than fp16
-// (per-row 8-bit quantization, see knn_filter.hip "int8 filter image"), so a
+// (per-row 8-bit quantization, see filter/tiled.inc "int8 filter image"), so a
 // k-th upper bound sits well above the k-th distance: after the last two
 // phases the k candidates with the smallest upper bounds are rescored exactly
 // (launch_exact_kth) and their largest exact composite becomes the threshold

@@ -188,7 +188,9 @@ int launch_final_select(const uint64_t* keys, int64_t nq, int64_t cap, const uin
                         int64_t alt_m, int64_t alt_gate, hipStream_t stream,
                         uint64_t* prune = nullptr);
 
-// Batched filter on the fp16 matrix cores (knn_filter.hip): appends every
+// Batched filter on the fp16 matrix cores (knn_filter.hip: the entry points
+// and the fp16 error bound; the kernels: filter/*.inc, compiled into the
+// variants knn_filter_q256.hip, _h256, _q128, _q64, _q64i): appends every
 // (row, query) whose rigorous lower bound reaches the query's threshold.
 struct FilterArgs {
   const void* X;          // [n][d] corpus shard (f32 or f16)
@@ -225,16 +227,16 @@ struct FilterArgs {
                           // 32 no append atomics, 64 no append stores
 };
 int launch_filter(const FilterArgs& a, int metric, hipStream_t stream);
-// the LDS-DMA ring variant (knn_filter.hip ring_kernel) with FX_FILTER_RING=1
-// (the register-staged kernel otherwise)
+// the LDS-DMA ring variant (filter/ring.inc ring_kernel) with FX_FILTER_RING=1
+// (the register-staged kernel, filter/staged.inc, otherwise)
 bool filter_ring();
-// filter images in MFMA fragment order (knn_filter.hip filter_img2_kernel);
+// filter images in MFMA fragment order (filter/img2.inc filter_img2_kernel);
 // FX_IMAGE_TILED=0: row-major
 bool image_tiled();
-// int8 filter images (knn_filter.hip): per row kI8RowInfo floats {w, 1/s,
+// int8 filter images (built in knn_filter.hip): per row kI8RowInfo floats {w, 1/s,
 // N/s, n2/s, 0...} (launch_image8), per query kI8QInfo floats {s_q, R', n_q^2,
 // |q|, 0...} (launch_qprep8); kI8Kappa bounds P/R' (the two query error terms,
-// see knn_filter.hip "int8 filter image")
+// see filter/tiled.inc "int8 filter image")
 constexpr int kI8RowInfo = 4;
 constexpr int kI8QInfo = 4;
 constexpr float kI8Kappa = 128.f;
@@ -265,6 +267,8 @@ int launch_qprep8(const float* Q, int64_t nq, int64_t nq_pad, int d, int dq, int
                   uint32_t* count = nullptr);
 int launch_qprep(const float* Q, int64_t nq, int64_t nq_pad, int d, int dq, int metric,
                  uint16_t* Qh, float* qinfo, hipStream_t stream);
+// rows per tile of every filter kernel (FilterArgs::tile_start ...)
+constexpr int kFilterTileRows = 256;
 int filter_tile_rows(int dtype);
 // fp16 filter image + row sums of squares of an f32 corpus (knn_filter.hip)
 int launch_image(const float* X, int64_t n, int d, void* img, float* rowinfo, hipStream_t stream);

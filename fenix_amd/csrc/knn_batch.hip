@@ -31,7 +31,7 @@
 namespace fx {
 
 // The fp32-MFMA batch kernel was replaced by the fp16-MFMA filter
-// (knn_filter.hip, 4-7x faster); it stays in diagnostic builds (tools/).
+// (knn_filter.hip and filter/, 4-7x faster); it stays in diagnostic builds (tools/).
 // The query norms and the exact rescoring below serve the filter.
 #ifdef FX_DIAG_BUILD
 #ifndef FX_BATCH_BQ

@@ -1,12 +1,41 @@
-// filter_img3_kernel with 64-query tiles (knn_filter.hip compiled again, K
-// chunks of 32 as the tiled images need): int8 filter images for batches of
+// The tiled-image kernels with 64-query tiles and K chunks of 32 (as the
+// tiled images need), namespace fx::q64i: int8 filter images for batches of
 // <= 64 queries, which a 256-query tile would multiply mostly as padding.
-// Only its tiled-image kernel is compiled (fp16 and f32 rows of <= 64
-// queries take the q64 build).
-#define FX_FILTER_VARIANT
+// Holds
+//   filter_img3_kernel<., false / true>   tiled fp16 / int8 images (filter/img3.inc)
+//   filter_img6_kernel<.>                 int8 images, a resident slice (filter/img6.inc)
+// and in diagnostic builds ring_kernel (filter/ring.inc); no register-staged
+// kernel (fp16 and f32 rows of <= 64 queries take the q64 variant).
+// launch_filter (knn_filter.hip) sends it the int8 images of batches of <= 64
+// queries: launch_img6() when the slice fits (img6_fits), else launch().
+#include "fx_internal.h"
+
+#include <type_traits>
+
 #define FX_FILTER_BQ 64
 #define FX_FILTER_BK 32
-#define FX_FILTER_ROWS 0  // the tiled-image kernel only
-#define FX_FILTER_IMG3 1
-#define FX_FILTER_IMPL q64i
-#include "knn_filter.hip"
+
+namespace fx {
+namespace q64i {
+
+#include "filter/tile.inc"
+#include "filter/tiled.inc"
+#include "filter/img3.inc"
+#include "filter/img6.inc"  // launch_img6(), img6_fits()
+#ifdef FX_DIAG_BUILD
+#include "filter/ring.inc"
+#endif
+
+int launch(const FilterArgs& a, int metric, hipStream_t stream) {
+  if (a.num_tiles <= 0) return FX_OK;
+  if (a.rowinfo != nullptr && image_tiled())  // the image in MFMA fragment order
+    return launch_img3(a, metric, stream);
+#ifdef FX_DIAG_BUILD
+  if (filter_ring()) return launch_ring_rows(a, metric, stream);
+#endif
+  set_error("filter: row type not compiled into this variant");
+  return FX_EUNSUPPORTED;
+}
+
+}  // namespace q64i
+}  // namespace fx

@@ -22,7 +22,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fenix_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
-SOURCES = ["knn_filter_q64i.hip", "knn_filter_q128.hip", "knn_filter.hip", "knn_code.hip"]
+# every filter variant (knn_filter.hip itself holds no MFMA kernel) and the coder
+SOURCES = ["knn_filter_q64i.hip", "knn_filter_q128.hip", "knn_filter_q256.hip",
+           "knn_filter_q64.hip", "knn_filter_h256.hip", "knn_code.hip"]
 
 
 @pytest.fixture(scope="module")
