@@ -1,482 +1,21 @@
-// extern "C" entry points declared in include/fenix_knn.h, plus the error and
-// device-property helpers the kernels' planners use.
-#include <stdarg.h>
-#include <stdlib.h>
-#include <stdio.h>
-#include <string.h>
-
+// extern "C" entry points declared in include/fenix_knn.h and the phase
+// drivers of the batched filter (plans: knn_plan.hip; errors, options and
+// device properties: fx_runtime.hip; the exact-scan entry points: capi_ex.hip).
 #include <atomic>
-#include <map>
-#include <set>
-#include <tuple>
-#include <vector>
-#include <mutex>
-#include <utility>
 
-#include "fx_internal.h"
+#include "fx_plan.h"
 
 namespace fx {
-
-static thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: %s", what, hipGetErrorString(e));
-    return FX_EHIP;
-  }
-  return FX_OK;
-}
-
-static std::mutex g_mu;
-
-// ----------------------------------------------------------------- options --
-static const char* const kOptNames[kOptCount] = {
-    "batched", "batch_min_queries", "batch_cap", "batch_sample_ratio",
-    "force_fallback", "scan_interleave", "q8_dma", "filter_image", "batch_ub_test",
-    "single_query_image", "i8_max_k", "img6", "img8", "i8_sample_ratio", "i8_grow_ratio",
-    "select_prune", "scan_stream"};
-static std::atomic<int64_t> g_opts[kOptCount] = {{1}, {2}, {0}, {0}, {0}, {-1}, {1}, {8}, {1}, {1},
-                                                 {1024}, {1}, {1}, {8}, {16}, {1}, {-1}};
-
-int64_t option(Option o) { return g_opts[o].load(std::memory_order_relaxed); }
-
-static int option_index(const char* name) {
-  if (name == nullptr) return -1;
-  for (int i = 0; i < kOptCount; ++i)
-    if (strcmp(name, kOptNames[i]) == 0) return i;
-  return -1;
-}
-
-#ifdef FX_DIAG_BUILD
-int diag_env(const char* name, int dflt) {
-  const char* env = getenv(name);
-  return env != nullptr ? atoi(env) : dflt;
-}
-#endif
 
 // host-blocking synchronisations performed (fx_host_sync_count); searches
 // perform none, and any added one must go through host_sync
 static std::atomic<uint64_t> g_host_syncs{0};
 
-int device_cus(int* out) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) {
-    set_error("hipGetDevice: %s", hipGetErrorString(e));
-    return FX_EHIP;
-  }
-  static std::map<int, int> cache;
-  std::lock_guard<std::mutex> lk(g_mu);
-  auto it = cache.find(dev);
-  if (it != cache.end()) {
-    *out = it->second;
-    return FX_OK;
-  }
-  int cus = 0;
-  e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) {
-    set_error("hipDeviceGetAttribute: %s", hipGetErrorString(e));
-    return FX_EHIP;
-  }
-  cache[dev] = cus;
-  *out = cus;
-  return FX_OK;
-}
-
-// The dynamic-LDS limit above 64 KB is a per-device function attribute: set
-// it once per (device, kernel), so a table sharded over several devices can
-// launch the same kernel on each of them.
-int allow_lds(const void* fn) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) {
-    set_error("hipGetDevice: %s", hipGetErrorString(e));
-    return FX_EHIP;
-  }
-  static std::set<std::pair<int, const void*>> done;
-  std::lock_guard<std::mutex> lk(g_mu);
-  if (!done.insert(std::make_pair(dev, fn)).second) return FX_OK;
-  // the dynamic share of the 160 KB: whatever the kernel's static __shared__
-  // variables leave
-  hipFuncAttributes at = {};
-  e = hipFuncGetAttributes(&at, fn);
-  if (e != hipSuccess) {
-    done.erase(std::make_pair(dev, fn));
-    set_error("hipFuncGetAttributes: %s", hipGetErrorString(e));
-    return FX_EHIP;
-  }
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          160 * 1024 - (int)at.sharedSizeBytes);
-  if (e != hipSuccess) {
-    done.erase(std::make_pair(dev, fn));
-    set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
-    return FX_EHIP;
-  }
-  return FX_OK;
-}
-
-int kernel_occupancy(const void* fn, int block, size_t smem, int* out) {
-  if (smem > 64 * 1024) {
-    int rc = allow_lds(fn);
-    if (rc) return rc;
-  }
-  int dev = 0;
-  hipError_t e0 = hipGetDevice(&dev);
-  if (e0 != hipSuccess) {
-    set_error("hipGetDevice: %s", hipGetErrorString(e0));
-    return FX_EHIP;
-  }
-  static std::map<std::tuple<int, const void*, size_t>, int> cache;
-  std::lock_guard<std::mutex> lk(g_mu);
-  auto key = std::make_tuple(dev, fn, smem);
-  auto it = cache.find(key);
-  if (it != cache.end()) {
-    *out = it->second;
-    return FX_OK;
-  }
-  int nb = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, block, smem);
-  if (e != hipSuccess) {
-    set_error("hipOccupancyMaxActiveBlocksPerMultiprocessor: %s", hipGetErrorString(e));
-    return FX_EHIP;
-  }
-  cache[key] = nb;
-  *out = nb;
-  return FX_OK;
-}
-
-static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-static int validate(int64_t n, int64_t d, int dtype, int64_t nq, int metric) {
-  if (n < 1 || d < 1 || nq < 1) {
-    set_error("invalid shape n=%lld d=%lld nq=%lld", (long long)n, (long long)d, (long long)nq);
-    return FX_EINVAL;
-  }
-  if (d > (1 << 20)) {
-    set_error("d=%lld too large", (long long)d);
-    return FX_EUNSUPPORTED;
-  }
-  if (dtype != FX_DTYPE_F32 && dtype != FX_DTYPE_F16) {
-    set_error("unsupported dtype %d", dtype);
-    return FX_EINVAL;
-  }
-  if (metric < FX_METRIC_L2 || metric > FX_METRIC_COS) {
-    set_error("unsupported metric %d", metric);
-    return FX_EINVAL;
-  }
-  return FX_OK;
-}
-
-static constexpr int64_t kMaxK = 1024;  // fused path; larger k: knn_large.hip
-static constexpr int64_t kLargeMaxK = 0x7fffffffll;
-
-// ---------------------------------------------------------------- batched --
-//
-// Batched queries (nq >= kBatchMinQ, f32) run the MFMA kernel of knn_batch.hip
-// in phases over growing row samples (L2: the GEMM gives |x|^2+|q|^2-2x.q,
-// rows pass on a rigorous fp32 lower bound and every appended candidate is
-// rescored exactly before any threshold or result is taken):
-//   phase 0: a sample of <= cap rows, no threshold -> every (row, query) kept;
-//   phase i: a sample ~cap/(4k) times larger, threshold = the k-th composite
-//            of phase i-1 (an upper bound of the global k-th: the k-th of any
-//            row subset is), so it keeps ~cap/4 candidates per query;
-//   last:    every row with the last threshold -> final select.
-// A query whose final candidates overflow `cap` is recomputed exactly by the
-// single-query scan, gated on the device (fx_knn_reduce: no host sync).
-static constexpr int64_t kListLen = 4096;  // candidate buffer viewed as lists
-// int8 filter image (filter_phases_i8): the final pass's sample F1 takes
-// every r1-th tile, the samples before it grow by r2 (options
-// "i8_sample_ratio", default 8, and "i8_grow_ratio", default 16)
-
-struct BatchLayout {
-  int64_t cap = 0, tiles = 0, nq_pad = 0;
-  int nphases = 0;
-  bool filter = false;  // fp16-MFMA filter + exact rescoring (knn_filter.hip)
-  bool img8 = false;    // planned for an int8 filter image (filter_phases_i8)
-  int dq = 0;
-  int64_t start[16], stride[16], num[16];
-  MergePlan merge;
-  size_t off_qnorm, off_thr, off_count, off_cand, off_merge, off_cand_ub, off_qh, off_qinfo,
-      off_topd, off_topr, off_prune, total;
-};
-
-// The fp16-MFMA filter (knn_filter.hip, kernels in filter/*.inc).  Diagnostic builds keep the
-// rejected fp32-MFMA batch kernel (knn_batch.hip) behind FX_BATCH_FILTER=0.
-static bool use_filter() { return diag_env("FX_BATCH_FILTER", 1) != 0; }
-
-// A single query over an f32 corpus of at least this many bytes takes the
-// batched path when an int8 filter image is supplied (the *_img8 entry
-// points, option "single_query_image"): 10M x 768 1.41 vs 4.34 ms; the
-// filter path's fixed cost (~0.25 ms of small launches) loses below ~2.4 GB
-static constexpr int64_t kSingleImageMinBytes = (int64_t)4 << 30;
-// Int8 images serve k <= option "i8_max_k" (1 024 = kMaxK, every k the
-// filter plans).  Round 3's 64 K slots overflowed at k = 1 000 (6.25M x 1536
-// fp16 IP, profiles/r03_f16_int8_image.log); with the 4x buffer (256 K slots
-// at k = 1 000), the pruned selects (select_kernel MODE 3) and the shared LDS
-// append segments, 60 single queries (normal, near, clustered corpus) kept
-// 94-122 K candidates, none overflowed, 1.67 vs 2.84 ms for the exact scan,
-// bit-identical (profiles/r06_k1000_sweep*.json); batches at k 300-1 000 are
-// faster too (profiles/r06_kbatch_i8_max_k.jsonl).
-static int64_t i8_max_k() { return option(kOptI8MaxK); }
-
-static bool use_batched(int64_t nq, int dtype, int metric, int64_t d, bool aligned, int64_t n,
-                        bool img8, int64_t k) {
-  if (option(kOptBatched) == 0) return false;
-  // 2 queries: 6.5 ms vs 2 x 4.5 ms (10Mx768); "batch_min_queries" = 1 also
-  // sends every single query through the filter
-  int64_t min_q = option(kOptBatchMinQ) >= 1 ? option(kOptBatchMinQ) : 2;
-  if (nq == 1 && img8 && k <= i8_max_k() && option(kOptSingleImage) != 0 && d % 8 == 0 &&
-      n * d * (dtype == FX_DTYPE_F32 ? 4 : 2) >= kSingleImageMinBytes)
-    min_q = 1;
-  if (!use_filter()) min_q = 8;  // the fp32-MFMA kernel breaks even with scans at ~8 queries
-  if (nq < min_q || !aligned) return false;
-  // the rescoring repeats the scan's 16-B slot order: f32 rows need d % 4 == 0,
-  // f16 rows d % 8 == 0 (and the fp16 filter: the fp32-MFMA kernel reads f32 only)
-  if (dtype == FX_DTYPE_F32) return d % 4 == 0;
-  return dtype == FX_DTYPE_F16 && d % 8 == 0 && use_filter();
-}
-
-static int plan_phases(BatchLayout* b, int64_t tr, int64_t r);
-
-static int plan_batched(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, BatchLayout* b,
-                        bool img8) {
-  b->filter = use_filter();
-  b->img8 = img8 && b->filter;
-  const int64_t tr = b->filter ? filter_tile_rows(dtype) : batch_tile_rows();
-  b->cap = 64 * k > 16384 ? 64 * k : 16384;
-  // int8 images: 4x the buffer.  Their bounds keep whole clusters of a
-  // clustered corpus against a generic query (10M x 768, x + 10 x0 per
-  // 1 000 rows, 256 cosine queries: median 10 K, largest 33 K candidates);
-  // every consumer reads only the count it was given (select_kernel streams
-  // any count), so the larger buffer costs memory, not time
-  if (b->img8) b->cap *= 4;
-  if (option(kOptBatchCap) >= 16 * k) b->cap = option(kOptBatchCap);  // test: small buffers
-  b->cap = (b->cap + kListLen - 1) / kListLen * kListLen;
-  b->tiles = (n + tr - 1) / tr;
-  // nested samples: phase i scans every stride_i-th tile, each stride a
-  // multiple of the next, so every sample contains the previous one and has
-  // at least k rows under the previous threshold; ~cap/4 appends per query.
-  int64_t r = b->cap / (4 * k);  // >= 16 for k <= 1024
-  {  // test switch: denser samples (never sparser)
-    const int64_t v = option(kOptBatchRatio);
-    if (v >= 2 && v < r) r = v;
-  }
-  int rc = plan_phases(b, tr, r);
-  if (rc) return rc;
-  rc = plan_merge(nq, b->cap / kListLen, kListLen, k, &b->merge);
-  if (rc) return rc;
-  size_t off = 0;
-  b->off_qnorm = off;
-  off += align256((size_t)nq * 4);
-  b->off_thr = off;
-  off += align256((size_t)nq * 8);
-  b->off_count = off;
-  off += align256((size_t)nq * 4 * kCountStride);
-  b->off_cand = off;
-  off += align256((size_t)nq * b->cap * 8);
-  b->off_merge = off;
-  off += align256(b->merge.ws_bytes);
-  if (b->filter) {
-    b->dq = filter_dq((int)d);
-    b->nq_pad = (nq + filter_query_pad(nq) - 1) / filter_query_pad(nq) * filter_query_pad(nq);
-    b->off_cand_ub = off;
-    off += align256((size_t)nq * b->cap * 8);
-    // fp16 query tiles, or int8 ones padded to 256 queries (int8 filter images)
-    const size_t q16 = (size_t)b->nq_pad * b->dq * 2, q8 = (size_t)((nq + 255) / 256 * 256) * b->dq;
-    b->off_qh = off;
-    off += align256(q16 > q8 ? q16 : q8);
-    b->off_qinfo = off;
-    off += align256((size_t)nq * 16);
-    // the k best candidates by upper bound (int8 images: exact thresholds)
-    b->off_topd = off;
-    off += align256((size_t)nq * k * 4);
-    b->off_topr = off;
-    off += align256((size_t)nq * k * 8);
-  }
-  // the selects' prune scratch (int8 plans at large k: select_prune_lists)
-  b->off_prune = off;
-  if (b->img8) off += align256(select_prune_bytes(nq, k, b->cap));
-  b->total = off;
-  return FX_OK;
-}
-
-// Nested row samples of the batched phases: phase i scans every stride_i-th
-// tile of tr rows, each stride a multiple r of the next, the first at most
-// cap rows, the last every tile.
-// The int8 image's plan (filter_phases_i8).  The image stores its rows in a
-// permuted order (image8_perm: a Weyl sequence over the corpus), so any
-// PREFIX of its tiles is an equidistributed sample of the corpus: the
-// samples are nested prefixes, read as contiguous runs.  The last sample F1
-// holds ceil(tiles / r1) tiles (F2 reads the rest), the ones before it
-// shrink by r2 (their appends stay far below cap: about r2 k upper bounds
-// per query), the first holds at most cap rows.  10M x 768, r1 = 8, r2 = 16:
-// 20, 306, 4 883 tiles, then F2's 34 180.
-static int plan_phases_i8(BatchLayout* b, int64_t tr, int64_t r1, int64_t r2) {
-  int64_t nums[16];
-  int m = 0;
-  nums[m++] = b->tiles;
-  int64_t r = r1;
-  while (nums[m - 1] * tr > b->cap) {
-    if (m >= 15) {
-      set_error("batched sampling plan too deep");
-      return FX_EUNSUPPORTED;
-    }
-    nums[m] = (nums[m - 1] + r - 1) / r;
-    ++m;
-    r = r2;
-  }
-  b->nphases = m;
-  for (int i = 0; i < m; ++i) {
-    b->num[i] = nums[m - 1 - i];
-    b->start[i] = 0;
-    b->stride[i] = 1;
-  }
-  return FX_OK;
-}
-
-static int plan_phases(BatchLayout* b, int64_t tr, int64_t r) {
-  int64_t strides[16];
-  int m = 0;
-  strides[m++] = 1;
-  while ((b->tiles + strides[m - 1] - 1) / strides[m - 1] * tr > b->cap) {
-    if (m >= 15) {
-      set_error("batched sampling plan too deep");
-      return FX_EUNSUPPORTED;
-    }
-    strides[m] = strides[m - 1] * r;
-    ++m;
-  }
-  b->nphases = m;
-  for (int i = 0; i < m; ++i) {
-    const int64_t st = strides[m - 1 - i];
-    b->stride[i] = st;
-    b->start[i] = 0;
-    b->num[i] = (b->tiles + st - 1) / st;
-  }
-  return FX_OK;
-}
-
-struct SearchLayout {
-  ScanPlan scan;
-  MergePlan merge;
-  size_t lists_bytes, total;
-  bool large = false;  // k > kMaxK: distance-mode scan + radix sort (knn_large.hip)
-  LargeLayout lg;
-  bool batched;
-  BatchLayout batch;
-  size_t single_off;   // batched: workspace of the overflow fallback
-  int64_t fb_queries;  // batched: queries per fallback round (scan + merge over fb_queries)
-};
-
-static int plan_single(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, int metric,
-                       bool aligned, SearchLayout* s) {
-  int rc = plan_scan(n, d, dtype, k, metric, aligned, &s->scan);
-  if (rc) return rc;
-  rc = plan_merge(nq, s->scan.nlists, k, k, &s->merge);
-  if (rc) return rc;
-  s->lists_bytes = align256((size_t)nq * s->scan.nlists * k * 8);
-  s->total = s->lists_bytes + s->merge.ws_bytes;
-  s->batched = false;
-  return FX_OK;
-}
-
-static int plan_large_search(int64_t n, int64_t d, int dtype, int64_t nq, int metric,
-                             bool aligned, SearchLayout* s) {
-  int rc = plan_scan(n, d, dtype, 1, metric, aligned, &s->scan);
-  if (rc) return rc;
-  s->large = true;
-  s->batched = false;
-  s->lg = plan_large(n, nq);
-  s->lists_bytes = 0;
-  s->total = s->lg.total;
-  return FX_OK;
-}
-
-// The overflow fallback of the batched path runs the single-query plan over
-// rounds of fq queries; its candidate lists take at most this many bytes.
-static constexpr size_t kFallbackListBytes = (size_t)256 << 20;
-
-// Its scan takes at most kFallbackBlocks blocks per query: the gated launch
-// covers every query of a round, and an empty block still occupies its CU's
-// LDS while it starts and exits (256 blocks x 256 queries of 10M x 768: 99 us
-// with nothing to do; 16 per query: a few us, and an overflowing query still
-// streams its rows from 16 CUs).
-// Small batches spread the same total over more workgroups per query (4 096
-// workgroups in all, at least 16 per query): a single query that overflows is
-// rescanned at the full scan's width (256 workgroups, ~4.4 ms for 10M x 768)
-// instead of by 16 CUs (~38 ms).
-static constexpr int64_t kFallbackBlocks = 16;
-static constexpr int64_t kFallbackTotalBlocks = 4096;
-
-static int plan_fallback(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, int metric,
-                         bool aligned, SearchLayout* s, int64_t* fq) {
-  int rc = plan_scan(n, d, dtype, k, metric, aligned, &s->scan);
-  if (rc) return rc;
-  const int64_t per_q = kFallbackTotalBlocks / (nq > 0 ? nq : 1);
-  limit_scan_blocks(&s->scan, n, per_q > kFallbackBlocks ? per_q : kFallbackBlocks);
-  const size_t per_query = (size_t)s->scan.nlists * k * 8;
-  int64_t f = (int64_t)(kFallbackListBytes / (per_query > 0 ? per_query : 1));
-  if (f > nq) f = nq;
-  if (f > 65535) f = 65535;
-  if (f < 1) f = 1;
-  *fq = f;
-  rc = plan_merge(f, s->scan.nlists, k, k, &s->merge);
-  if (rc) return rc;
-  s->lists_bytes = align256((size_t)f * s->scan.nlists * k * 8);
-  s->total = s->lists_bytes + s->merge.ws_bytes;
-  s->batched = false;
-  return FX_OK;
-}
-
-// img8: the call supplies an int8 filter image (single queries may take
-// the batched path, use_batched); the reduce must plan with the same flag
-static int plan_search(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, int metric,
-                       bool aligned, SearchLayout* s, bool img8 = false) {
-  if (k > kMaxK) return plan_large_search(n, d, dtype, nq, metric, aligned, s);
-  if (!use_batched(nq, dtype, metric, d, aligned, n, img8, k)) {
-    return plan_single(n, d, dtype, nq, k, metric, aligned, s);
-  }
-  // the single-query plan over fb_queries queries serves overflowing queries
-  int64_t fq = 1;
-  int rc = plan_fallback(n, d, dtype, nq, k, metric, aligned, s, &fq);
-  if (rc) return rc;
-  const size_t single_total = s->total;
-  rc = plan_batched(n, d, dtype, nq, k, &s->batch,
-                    img8 && k <= i8_max_k() && d % 8 == 0 &&
-                        (dtype == FX_DTYPE_F32 || dtype == FX_DTYPE_F16));
-  if (rc) return rc;
-  s->batched = true;
-  s->fb_queries = fq;
-  s->single_off = s->batch.total;
-  s->total = s->batch.total + single_total;
-  return FX_OK;
-}
-
-
 // The fallback scan's arguments: top-k lists into ws, each workgroup gated
 // on its query's count (> gate_cap: recompute)
-static ScanArgs fallback_args(const SearchLayout& s, const void* corpus, int64_t n, int64_t d,
-                              int64_t row_base, int64_t k, const uint32_t* mask, int64_t gate_cap,
-                              char* ws) {
-  ScanArgs a = {};
-  a.X = corpus;
-  a.n = n;
-  a.d = (int)d;
-  a.row_base = row_base;
-  a.mask = mask;
-  a.rows_per_block = s.scan.rows_per_block;
-  a.k = (int)k;
-  a.cap = s.scan.cap;
-  a.qbytes = s.scan.qbytes;
-  a.mode = kModeTopk;
+static ScanArgs fallback_args(const SearchLayout& s, const fx_corpus& c, int64_t k,
+                              const uint32_t* mask, int64_t gate_cap, char* ws) {
+  ScanArgs a = scan_args(s.scan, c, nullptr, 0, mask, k, kModeTopk);
   a.out_lists = reinterpret_cast<uint64_t*>(ws);
   a.gate_cap = gate_cap;
   return a;
@@ -484,11 +23,10 @@ static ScanArgs fallback_args(const SearchLayout& s, const void* corpus, int64_t
 
 // The fallback's gated scan alone over all nq queries (s.fb_queries >= nq):
 // per overflowing query nlists lists of k composites at *lists, [nq][nlists k]
-static int fallback_scan(const SearchLayout& s, const void* corpus, int64_t n, int64_t d,
-                         int64_t row_base, const float* queries, int64_t nq, int64_t k,
-                         const uint32_t* mask, const uint32_t* count, int64_t gate_cap, char* ws,
-                         hipStream_t st, const uint64_t** lists) {
-  ScanArgs a = fallback_args(s, corpus, n, d, row_base, k, mask, gate_cap, ws);
+static int fallback_scan(const SearchLayout& s, const fx_corpus& c, const float* queries,
+                         int64_t nq, int64_t k, const uint32_t* mask, const uint32_t* count,
+                         int64_t gate_cap, char* ws, hipStream_t st, const uint64_t** lists) {
+  ScanArgs a = fallback_args(s, c, k, mask, gate_cap, ws);
   a.q = queries;
   a.gate = count;
   *lists = a.out_lists;
@@ -501,17 +39,14 @@ static int fallback_scan(const SearchLayout& s, const void* corpus, int64_t n, i
 // each workgroup reads its query's count and returns at once when it did not
 // overflow, so nothing waits for the host; the merge writes only the
 // recomputed queries' results.
-static int fallback_search(const SearchLayout& s, const void* corpus, int dtype, int64_t n,
-                           int64_t d, int64_t row_base, const float* queries, int64_t nq,
-                           int metric, int64_t k, const uint32_t* mask, const uint32_t* count,
+static int fallback_search(const SearchLayout& s, const fx_corpus& c, const float* queries,
+                           int64_t nq, int64_t k, const uint32_t* mask, const uint32_t* count,
                            int64_t gate_cap, char* ws, float* out_dist, int64_t* out_row,
                            hipStream_t st) {
-  (void)dtype;
-  (void)metric;
-  ScanArgs a = fallback_args(s, corpus, n, d, row_base, k, mask, gate_cap, ws);
+  ScanArgs a = fallback_args(s, c, k, mask, gate_cap, ws);
   for (int64_t q0 = 0; q0 < nq; q0 += s.fb_queries) {
     const int64_t qn = (nq - q0) < s.fb_queries ? (nq - q0) : s.fb_queries;
-    a.q = queries + (size_t)q0 * d;
+    a.q = queries + (size_t)q0 * c.d;
     a.gate = count + (size_t)q0 * kCountStride;
     int rc = launch_scan(s.scan, a, qn, st);
     if (rc) return rc;
@@ -532,17 +67,9 @@ static int fallback_search(const SearchLayout& s, const void* corpus, int dtype,
 // of the exact keys and recomputes overflowing queries.
 // With an fp16 filter image of an f32 corpus (fx_filter_image) the phases
 // stream the image (half the bytes) and the rescoring reads the f32 rows.
-//
-// An int8 filter image (fx_filter_image8) gives bounds ~30x wider than fp16
-// (per-row 8-bit quantization, see filter/tiled.inc "int8 filter image"), so a
-// k-th upper bound sits well above the k-th distance: after the last two
-// phases the k candidates with the smallest upper bounds are rescored exactly
-// (launch_exact_kth) and their largest exact composite becomes the threshold
-// (k scan distances lie at or below it), and the samples grow by
-// kI8SampleRatio per phase, which keeps the appends below cap/4 per query
-// (10M x 768 cosine, 256 queries: ~2.5 K, 6 K, 10 K, 4 K per phase).
+// (An int8 filter image has phases of its own: filter_phases_i8.)
 static int filter_phases(const BatchLayout& b, const void* X, int dtype, const void* image,
-                         const float* rowinfo, bool img8, int64_t n, int64_t d, int64_t row_base,
+                         const float* rowinfo, int64_t n, int64_t d, int64_t row_base,
                          const float* Q, int64_t nq, int metric, int64_t k,
                          const uint32_t* mask, char* w, hipStream_t st) {
   float* qnorm = reinterpret_cast<float*>(w + b.off_qnorm);
@@ -552,10 +79,7 @@ static int filter_phases(const BatchLayout& b, const void* X, int dtype, const v
   uint64_t* cand_ub = reinterpret_cast<uint64_t*>(w + b.off_cand_ub);
   uint16_t* qh = reinterpret_cast<uint16_t*>(w + b.off_qh);
   float* qinfo = reinterpret_cast<float*>(w + b.off_qinfo);
-  const int64_t nq_pad8 = (nq + 255) / 256 * 256;
-  int rc = img8 ? launch_qprep8(Q, nq, nq_pad8, (int)d, b.dq, metric,
-                                reinterpret_cast<int8_t*>(qh), qinfo, st)
-                : launch_qprep(Q, nq, b.nq_pad, (int)d, b.dq, metric, qh, qinfo, st);
+  int rc = launch_qprep(Q, nq, b.nq_pad, (int)d, b.dq, metric, qh, qinfo, st);
   if (rc) return rc;
   if (metric == FX_METRIC_COS) {  // the scan's max(|q|, 1e-12) for the rescoring
     rc = launch_qnorm(Q, nq, (int)d, qnorm, st, 0);
@@ -579,8 +103,7 @@ static int filter_phases(const BatchLayout& b, const void* X, int dtype, const v
     a.row_base = row_base;
     a.Qh = qh;
     a.dq = b.dq;
-    a.qstride = img8 ? nq_pad8 : b.nq_pad;
-    a.img8 = img8 ? 1 : 0;
+    a.qstride = b.nq_pad;
     a.all_pass = ph == 0 ? 1 : 0;  // (thr was just filled with the empty key)
     // sampling phases need only the k smallest upper bounds of their rows:
     // the k rows behind the previous threshold are in this (nested) sample
@@ -601,20 +124,6 @@ static int filter_phases(const BatchLayout& b, const void* X, int dtype, const v
     a.diag = diag_env("FX_FILTER_DIAG", 0);
     rc = launch_filter(a, metric, st);
     if (rc) return rc;
-    // int8 images, the last two phases: the exact distances of the k best
-    // upper bounds give the next threshold (earlier, small samples: the k-th
-    // upper bound, like fp16; their appends stay far below cap)
-    if (img8 && ph + 2 >= b.nphases) {
-      float* topd = reinterpret_cast<float*>(w + b.off_topd);
-      int64_t* topr = reinterpret_cast<int64_t*>(w + b.off_topr);
-      rc = run_merge(b.merge, last ? cand_ub : cand, nq, k, w + b.off_merge, topd, topr, st,
-                     nullptr, nullptr, 0, count, !last);
-      if (rc) return rc;
-      rc = launch_exact_kth(X, dtype, n, (int)d, row_base, Q, qnorm, nq, (int)k, topr, metric,
-                            thr, st);
-      if (rc) return rc;
-      continue;
-    }
     // the k-th upper bound of this phase's candidates: next threshold
     rc = run_merge(b.merge, last ? cand_ub : cand, nq, k, w + b.off_merge, nullptr, nullptr, st,
                    thr, nullptr, 0, count, !last);
@@ -703,8 +212,8 @@ static int filter_phases_i8(const BatchLayout& b, const void* X, int dtype, cons
   auto exact_threshold = [&](const uint64_t* keys, bool zero, const uint64_t* gate = nullptr,
                              int64_t gate_num = 0, int64_t gate_den = 1) {
     return launch_exact_threshold(X, dtype, n, (int)d, row_base, Q, qnorm, nq, keys, b.cap, count,
-                                  zero, (int)k, metric, thr, st, prune, topr, gate, gate_num,
-                                  gate_den);
+                                  zero, (int)k, metric, thr, st, prune, b.prune_lists, topr, gate,
+                                  gate_num, gate_den);
   };
   const int m = b.nphases;
   for (int ph = 0; ph + 2 < m; ++ph) {  // sampling phases: thresholds only
@@ -716,7 +225,7 @@ static int filter_phases_i8(const BatchLayout& b, const void* X, int dtype, cons
     // (both reset the counts they read: the next phase appends from 0)
     rc = ph + 3 == m ? exact_threshold(cand, true)
                      : launch_sample_threshold(cand, nq, b.cap, count, true, (int)k, thr, st,
-                                               prune);
+                                               prune, b.prune_lists);
     if (rc) return rc;
   }
   // F1: the last sample's tiles (with one phase: every tile), both bounds
@@ -818,32 +327,11 @@ extern "C" {
 
 int fx_version(void) { return 104; }
 
-const char* fx_last_error(void) { return g_err; }
+const char* fx_last_error(void) { return last_error(); }
 
-int fx_set_option(const char* name, int64_t value) {
-  const int i = option_index(name);
-  if (i < 0) {
-    set_error("unknown option %s", name ? name : "(null)");
-    return FX_EINVAL;
-  }
-  if (i == kOptI8MaxK && (value < 0 || value > kSelectMaxK)) {
-    set_error("option i8_max_k=%lld outside [0, %d] (the select kernel's LDS bound)",
-              (long long)value, kSelectMaxK);
-    return FX_EINVAL;
-  }
-  g_opts[i].store(value, std::memory_order_relaxed);
-  return FX_OK;
-}
+int fx_set_option(const char* name, int64_t value) { return set_option(name, value); }
 
-int fx_get_option(const char* name, int64_t* out) {
-  const int i = option_index(name);
-  if (i < 0 || out == nullptr) {
-    set_error("unknown option %s", name ? name : "(null)");
-    return FX_EINVAL;
-  }
-  *out = g_opts[i].load(std::memory_order_relaxed);
-  return FX_OK;
-}
+int fx_get_option(const char* name, int64_t* out) { return get_option(name, out); }
 
 uint64_t fx_host_sync_count(void) { return g_host_syncs.load(std::memory_order_relaxed); }
 
@@ -872,12 +360,8 @@ int fx_knn_workspace_bytes_img8(int64_t n, int64_t d, int dtype, int64_t nq, int
     set_error("out_bytes is null");
     return FX_EINVAL;
   }
-  int rc = validate(n, d, dtype, nq, 0);
+  int rc = validate(n, d, dtype, nq, k, FX_METRIC_L2, false);
   if (rc) return rc;
-  if (k < 1 || k > kLargeMaxK) {
-    set_error("k=%lld outside [1, %lld]", (long long)k, (long long)kLargeMaxK);
-    return FX_EUNSUPPORTED;
-  }
   size_t best = 0;
   for (int metric = 0; metric < 3; ++metric) {
     for (int aligned = 0; aligned < 2; ++aligned) {
@@ -885,7 +369,7 @@ int fx_knn_workspace_bytes_img8(int64_t n, int64_t d, int dtype, int64_t nq, int
       // i8_max_k): the larger of both; without one, the image-free plan only
       for (int with8 = 0; with8 < (img8 ? 2 : 1); ++with8) {
         SearchLayout s;
-        rc = plan_search(n, d, dtype, nq, k, metric, aligned != 0, &s, with8 != 0);
+        rc = plan_search(n, d, dtype, nq, k, metric, aligned != 0, with8 != 0, &s);
         if (rc) return rc;
         if (s.total > best) best = s.total;
       }
@@ -895,21 +379,20 @@ int fx_knn_workspace_bytes_img8(int64_t n, int64_t d, int dtype, int64_t nq, int
   return FX_OK;
 }
 
-static int search_layout(const void* corpus, int dtype, int64_t n, int64_t d, int64_t nq,
-                         int metric, int64_t k, void* ws, size_t ws_bytes, SearchLayout* s,
-                         bool img8 = false) {
-  int rc = validate(n, d, dtype, nq, metric);
+}  // extern "C"
+
+// One call's plan: arguments checked (shape, k, then null pointers), planned
+// once from the options as they are now, and held against the workspace the
+// call brought.  img8: the call supplies an int8 filter image.
+static int search_layout(const fx_corpus& c, int64_t nq, int metric, int64_t k, bool img8,
+                         const void* ws, size_t ws_bytes, SearchLayout* s) {
+  int rc = validate(c.n, c.d, c.dtype, nq, k, metric, false);
   if (rc) return rc;
-  if (k < 1 || k > kLargeMaxK) {
-    set_error("k=%lld outside [1, %lld]", (long long)k, (long long)kLargeMaxK);
-    return FX_EUNSUPPORTED;
-  }
-  if (!corpus || !ws) {
+  if (!c.data || !ws) {
     set_error("null pointer argument");
     return FX_EINVAL;
   }
-  const bool aligned = ((uintptr_t)corpus % 16) == 0;
-  rc = plan_search(n, d, dtype, nq, k, metric, aligned, s, img8);
+  rc = plan_search(c.n, c.d, c.dtype, nq, k, metric, ((uintptr_t)c.data % 16) == 0, img8, s);
   if (rc) return rc;
   if (ws_bytes < s->total) {
     set_error("workspace too small: %zu < %zu", ws_bytes, s->total);
@@ -918,97 +401,136 @@ static int search_layout(const void* corpus, int dtype, int64_t n, int64_t d, in
   return FX_OK;
 }
 
-}  // extern "C"
-
 // a filter image applies to rows of whole 16-B pieces (d % 8 == 0) through
-// the filter: an fp16 image to f32 rows, an int8 image to f32 or f16 rows
-static bool image_applies(const SearchLayout& s, int dtype, int64_t d, bool img8, int64_t k) {
-  if (img8 && k > i8_max_k()) return false;
-  return s.batched && s.batch.filter && d % 8 == 0 &&
-         (dtype == FX_DTYPE_F32 || (img8 && dtype == FX_DTYPE_F16));
+// the filter: an int8 image where the plan took it (BatchLayout::img8, f32 or
+// f16 rows), an fp16 image to f32 rows
+static bool image_applies(const SearchLayout& s, const fx_corpus& c, bool img8) {
+  if (!s.batched || !s.batch.filter) return false;
+  return img8 ? s.batch.img8 : c.d % 8 == 0 && c.dtype == FX_DTYPE_F32;
 }
 
-static int scan_impl(const void* corpus, int dtype, int64_t n, int64_t d, int64_t row_base,
-                     const void* image, const float* rowinfo, bool img8, const float* queries,
-                     int64_t nq, int metric, int64_t k, const uint32_t* mask, void* ws,
-                     size_t ws_bytes, void* stream) {
-  SearchLayout s;
-  int rc = search_layout(corpus, dtype, n, d, nq, metric, k, ws, ws_bytes, &s,
-                         img8 && image != nullptr);
-  if (rc) return rc;
+static int scan_impl(const SearchLayout& s, const fx_corpus& c, const void* image,
+                     const float* rowinfo, bool img8, const float* queries, int64_t nq,
+                     int metric, int64_t k, const uint32_t* mask, void* ws, hipStream_t st) {
   if (!queries) {
     set_error("null pointer argument");
     return FX_EINVAL;
   }
-  if (row_base < 0 || row_base + n >= 0xffffffffll) {
-    set_error("global rows [%lld, %lld) exceed the 32-bit row space", (long long)row_base,
-              (long long)(row_base + n));
+  if (c.row_base < 0 || c.row_base + c.n >= 0xffffffffll) {
+    set_error("global rows [%lld, %lld) exceed the 32-bit row space", (long long)c.row_base,
+              (long long)(c.row_base + c.n));
     return FX_EUNSUPPORTED;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* w = reinterpret_cast<char*>(ws);
   if (s.batched) {
     if (s.batch.filter) {
-      const bool img = image != nullptr && image_applies(s, dtype, d, img8, k);
+      const bool img = image != nullptr && image_applies(s, c, img8);
       if (img && (rowinfo == nullptr || (uintptr_t)image % 16 != 0)) {
         set_error("filter image: null row info or image not 16-byte aligned");
         return FX_EINVAL;
       }
-      if (img && img8) {  // int8 image: denser samples (filter_phases)
-        BatchLayout b = s.batch;
-        const int64_t rmax = b.cap / (4 * k);
-        const int64_t o1 = option(kOptI8SampleRatio) >= 2 ? option(kOptI8SampleRatio) : 2;
-        const int64_t o2 = option(kOptI8GrowRatio) >= 2 ? option(kOptI8GrowRatio) : 2;
-        int64_t r1 = rmax < o1 ? rmax : o1;
-        int64_t r2 = rmax < o2 ? rmax : o2;
-        const int64_t v = option(kOptBatchRatio);  // test switch: any ratio up to rmax
-        if (v >= 2) r1 = r2 = v < rmax ? v : rmax;
-        rc = plan_phases_i8(&b, filter_tile_rows(dtype), r1, r2);
-        if (rc) return rc;
-        return filter_phases_i8(b, corpus, dtype, image, rowinfo, n, d, row_base, queries, nq,
-                                metric, k, mask, reinterpret_cast<char*>(ws), st);
-      }
-      return filter_phases(s.batch, corpus, dtype, img ? image : nullptr, rowinfo, false, n, d,
-                           row_base, queries, nq, metric, k, mask, reinterpret_cast<char*>(ws),
-                           st);
+      if (img && img8)
+        return filter_phases_i8(s.batch, c.data, c.dtype, image, rowinfo, c.n, c.d, c.row_base,
+                                queries, nq, metric, k, mask, w, st);
+      return filter_phases(s.batch, c.data, c.dtype, img ? image : nullptr, rowinfo, c.n, c.d,
+                           c.row_base, queries, nq, metric, k, mask, w, st);
     }
 #ifdef FX_DIAG_BUILD
-    return batched_phases(s.batch, reinterpret_cast<const float*>(corpus), n, d, row_base,
-                          queries, nq, metric, k, mask, reinterpret_cast<char*>(ws), st);
+    return batched_phases(s.batch, reinterpret_cast<const float*>(c.data), c.n, c.d, c.row_base,
+                          queries, nq, metric, k, mask, w, st);
 #endif
   }
   if (s.large) {
-    ScanArgs a = {};
-    a.X = corpus;
-    a.n = n;
-    a.d = (int)d;
-    a.row_base = row_base;
-    a.mask = mask;
-    a.rows_per_block = s.scan.rows_per_block;
-    a.cap = s.scan.cap;
-    a.qbytes = s.scan.qbytes;
+    ScanArgs a = scan_args(s.scan, c, nullptr, 0, mask, 1, kModeDist);
     a.q = queries;
-    return large_scan(s.scan, a, nq, s.lg, reinterpret_cast<char*>(ws), st);
+    return large_scan(s.scan, a, nq, s.lg, w, st);
   }
-  uint64_t* lists = reinterpret_cast<uint64_t*>(ws);
-  ScanArgs a = {};
-  a.X = corpus;
-  a.n = n;
-  a.d = (int)d;
-  a.row_base = row_base;
-  a.mask = mask;
-  a.rows_per_block = s.scan.rows_per_block;
-  a.k = (int)k;
-  a.cap = s.scan.cap;
-  a.qbytes = s.scan.qbytes;
-  a.mode = kModeTopk;
-  for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
-    const int64_t qn = (nq - q0) < 65535 ? (nq - q0) : 65535;
-    a.q = queries + (size_t)q0 * d;
-    a.out_lists = lists + (size_t)q0 * s.scan.nlists * k;
-    rc = launch_scan(s.scan, a, qn, st);
+  ScanArgs a = scan_args(s.scan, c, nullptr, 0, mask, k, kModeTopk);
+  a.q = queries;
+  a.out_lists = reinterpret_cast<uint64_t*>(ws);
+  return launch_scan_queries(s.scan, a, nq, st);
+}
+
+// The scan half of a search call: plan, then run (fx_knn_scan*)
+static int scan_call(const fx_corpus& c, const void* image, const float* rowinfo, bool img8,
+                     const float* queries, int64_t nq, int metric, int64_t k,
+                     const uint32_t* mask, void* ws, size_t ws_bytes, void* stream) {
+  SearchLayout s;
+  int rc = search_layout(c, nq, metric, k, img8 && image != nullptr, ws, ws_bytes, &s);
+  if (rc) return rc;
+  return scan_impl(s, c, image, rowinfo, img8, queries, nq, metric, k, mask, ws,
+                   reinterpret_cast<hipStream_t>(stream));
+}
+
+static int reduce_impl(const SearchLayout& s, const fx_corpus& c, const float* queries,
+                       int64_t nq, int64_t k, const uint32_t* mask, void* ws, float* out_dist,
+                       int64_t* out_row, hipStream_t st) {
+  if (!out_dist || !out_row) {
+    set_error("null pointer argument");
+    return FX_EINVAL;
+  }
+  char* w = reinterpret_cast<char*>(ws);
+  if (s.large) return large_reduce(c.n, nq, k, s.lg, w, out_dist, out_row, st);
+  if (!s.batched) {
+    const uint64_t* lists = reinterpret_cast<const uint64_t*>(ws);
+    return run_merge(s.merge, lists, nq, k, w + s.lists_bytes, out_dist, out_row, st);
+  }
+  // batched: final select over the last phase's candidates
+  const BatchLayout& b = s.batch;
+  const uint64_t* cand = reinterpret_cast<const uint64_t*>(w + b.off_cand);
+  uint32_t* count = reinterpret_cast<uint32_t*>(w + b.off_count);
+  uint64_t* prune = reinterpret_cast<uint64_t*>(w + b.off_prune);
+  // queries whose candidates overflowed `cap` are recomputed exactly, gated
+  // on the device ("force_fallback" (test switch): every query)
+  const int64_t gate_cap = option(kOptForceFallback) != 0 ? -1 : b.cap;
+  int rc;
+  if (b.img8 && s.fb_queries >= nq) {
+    // one round: the gated scan's lists feed the final select of the
+    // overflowing queries (no merge levels of their own)
+    const uint64_t* lists = nullptr;
+    rc = fallback_scan(s, c, queries, nq, k, mask, count, gate_cap, w + s.single_off, st, &lists);
     if (rc) return rc;
+    return launch_final_select(cand, nq, b.cap, count, (int)k, out_dist, out_row, lists,
+                               s.scan.nlists * k, gate_cap, st, prune, b.prune_lists);
   }
-  return FX_OK;
+  // (the fallback gate reads the counts next: kept)
+  rc = b.img8 ? launch_final_select(cand, nq, b.cap, count, (int)k, out_dist, out_row, nullptr, 0,
+                                    0, st, prune, b.prune_lists)
+              : run_merge(b.merge, cand, nq, k, w + b.off_merge, out_dist, out_row, st, nullptr,
+                          nullptr, 0, count);
+  if (rc) return rc;
+  return fallback_search(s, c, queries, nq, k, mask, count, gate_cap, w + s.single_off, out_dist,
+                         out_row, st);
+}
+
+// The reduce half of a search call (fx_knn_reduce*): its own plan, which
+// equals the scan half's as long as no option changed in between
+static int reduce_call(const fx_corpus& c, bool img8, const float* queries, int64_t nq, int metric,
+                       int64_t k, const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
+                       int64_t* out_row, void* stream) {
+  SearchLayout s;
+  int rc = search_layout(c, nq, metric, k, img8, ws, ws_bytes, &s);
+  if (rc) return rc;
+  return reduce_impl(s, c, queries, nq, k, mask, ws, out_dist, out_row,
+                     reinterpret_cast<hipStream_t>(stream));
+}
+
+// A whole search (fx_knn_search*): one plan runs both halves
+static int search_call(const fx_corpus& c, const void* image, const float* rowinfo, bool img8,
+                       const float* queries, int64_t nq, int metric, int64_t k,
+                       const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
+                       int64_t* out_row, void* stream) {
+  if (!out_dist || !out_row) {
+    set_error("null pointer argument");
+    return FX_EINVAL;
+  }
+  SearchLayout s;
+  int rc = search_layout(c, nq, metric, k, img8 && image != nullptr, ws, ws_bytes, &s);
+  if (rc) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  rc = scan_impl(s, c, image, rowinfo, img8, queries, nq, metric, k, mask, ws, st);
+  if (rc) return rc;
+  return reduce_impl(s, c, queries, nq, k, mask, ws, out_dist, out_row, st);
 }
 
 extern "C" {
@@ -1016,24 +538,24 @@ extern "C" {
 int fx_knn_scan(const void* corpus, int dtype, int64_t n, int64_t d, int64_t row_base,
                 const float* queries, int64_t nq, int metric, int64_t k,
                 const uint32_t* mask, void* ws, size_t ws_bytes, void* stream) {
-  return scan_impl(corpus, dtype, n, d, row_base, nullptr, nullptr, false, queries, nq, metric, k,
-                   mask, ws, ws_bytes, stream);
+  return scan_call(corpus_of(corpus, dtype, n, d, row_base), nullptr, nullptr, false, queries, nq, metric,
+                   k, mask, ws, ws_bytes, stream);
 }
 
 int fx_knn_scan_img(const void* corpus, int dtype, int64_t n, int64_t d, int64_t row_base,
                     const void* image, const float* rowinfo, const float* queries, int64_t nq,
                     int metric, int64_t k, const uint32_t* mask, void* ws, size_t ws_bytes,
                     void* stream) {
-  return scan_impl(corpus, dtype, n, d, row_base, image, rowinfo, false, queries, nq, metric, k,
-                   mask, ws, ws_bytes, stream);
+  return scan_call(corpus_of(corpus, dtype, n, d, row_base), image, rowinfo, false, queries, nq, metric,
+                   k, mask, ws, ws_bytes, stream);
 }
 
 int fx_knn_scan_img8(const void* corpus, int dtype, int64_t n, int64_t d, int64_t row_base,
                      const void* image, const float* rowinfo, const float* queries, int64_t nq,
                      int metric, int64_t k, const uint32_t* mask, void* ws, size_t ws_bytes,
                      void* stream) {
-  return scan_impl(corpus, dtype, n, d, row_base, image, rowinfo, true, queries, nq, metric, k,
-                   mask, ws, ws_bytes, stream);
+  return scan_call(corpus_of(corpus, dtype, n, d, row_base), image, rowinfo, true, queries, nq, metric,
+                   k, mask, ws, ws_bytes, stream);
 }
 
 int fx_filter_image_bytes(int64_t n, int64_t d, size_t* image_bytes, size_t* rowinfo_bytes) {
@@ -1133,69 +655,16 @@ int fx_filter_image_used(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k,
     return FX_EINVAL;
   }
   *out = 0;
-  int rc = validate(n, d, dtype, nq, metric);
+  int rc = validate(n, d, dtype, nq, k, metric, false);
   if (rc) return rc;
-  if (k < 1 || k > kLargeMaxK) {
-    set_error("k=%lld outside [1, %lld]", (long long)k, (long long)kLargeMaxK);
-    return FX_EUNSUPPORTED;
-  }
   SearchLayout s;
   // (the int8 image, the host's default, also serves single queries over
   // large corpora: use_batched)
   const bool img8 = option(kOptFilterImage) == 8;
-  rc = plan_search(n, d, dtype, nq, k, metric, true, &s, img8);
+  rc = plan_search(n, d, dtype, nq, k, metric, true, img8, &s);
   if (rc) return rc;
-  *out = image_applies(s, dtype, d, img8, k) ? 1 : 0;
+  *out = image_applies(s, corpus_of(nullptr, dtype, n, d, 0), img8) ? 1 : 0;
   return FX_OK;
-}
-
-static int reduce_impl(const void* corpus, int dtype, int64_t n, int64_t d, int64_t row_base,
-                       const float* queries, int64_t nq, int metric, int64_t k,
-                       const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
-                       int64_t* out_row, void* stream, bool img8) {
-  SearchLayout s;
-  int rc = search_layout(corpus, dtype, n, d, nq, metric, k, ws, ws_bytes, &s, img8);
-  if (rc) return rc;
-  if (!out_dist || !out_row) {
-    set_error("null pointer argument");
-    return FX_EINVAL;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (s.large) {
-    return large_reduce(n, nq, k, s.lg, reinterpret_cast<char*>(ws), out_dist, out_row, st);
-  }
-  if (!s.batched) {
-    const uint64_t* lists = reinterpret_cast<const uint64_t*>(ws);
-    void* mws = reinterpret_cast<char*>(ws) + s.lists_bytes;
-    return run_merge(s.merge, lists, nq, k, mws, out_dist, out_row, st);
-  }
-  // batched: final select over the last phase's candidates
-  const BatchLayout& b = s.batch;
-  char* w = reinterpret_cast<char*>(ws);
-  const uint64_t* cand = reinterpret_cast<const uint64_t*>(w + b.off_cand);
-  uint32_t* count = reinterpret_cast<uint32_t*>(w + b.off_count);
-  // queries whose candidates overflowed `cap` are recomputed exactly, gated
-  // on the device ("force_fallback" (test switch): every query)
-  const int64_t gate_cap = option(kOptForceFallback) != 0 ? -1 : b.cap;
-  if (b.img8 && s.fb_queries >= nq) {
-    // one round: the gated scan's lists feed the final select of the
-    // overflowing queries (no merge levels of their own)
-    const uint64_t* lists = nullptr;
-    rc = fallback_scan(s, corpus, n, d, row_base, queries, nq, k, mask, count, gate_cap,
-                       w + s.single_off, st, &lists);
-    if (rc) return rc;
-    return launch_final_select(cand, nq, b.cap, count, (int)k, out_dist, out_row, lists,
-                               s.scan.nlists * k, gate_cap, st,
-                               reinterpret_cast<uint64_t*>(w + b.off_prune));
-  }
-  // (the fallback gate reads the counts next: kept)
-  rc = b.img8 ? launch_final_select(cand, nq, b.cap, count, (int)k, out_dist, out_row, nullptr, 0,
-                                    0, st, reinterpret_cast<uint64_t*>(w + b.off_prune))
-              : run_merge(b.merge, cand, nq, k, w + b.off_merge, out_dist, out_row, st, nullptr,
-                          nullptr, 0, count);
-  if (rc) return rc;
-  return fallback_search(s, corpus, dtype, n, d, row_base, queries, nq, metric, k, mask, count,
-                         gate_cap, w + s.single_off, out_dist, out_row, st);
 }
 
 int fx_knn_filter_state(const void* corpus, int dtype, int64_t n, int64_t d, int64_t nq,
@@ -1203,8 +672,8 @@ int fx_knn_filter_state(const void* corpus, int dtype, int64_t n, int64_t d, int
                         uint64_t* out_thr, uint64_t* out_cand, uint64_t* out_cand_ub,
                         void* stream) {
   SearchLayout s;
-  int rc = search_layout(corpus, dtype, n, d, nq, metric, k, const_cast<void*>(ws), ws_bytes, &s,
-                         img8 != 0);
+  int rc = search_layout(corpus_of(corpus, dtype, n, d, 0), nq, metric, k, img8 != 0, ws,
+                         ws_bytes, &s);
   if (rc) return rc;
   if (!s.batched || !s.batch.filter) {
     set_error("fx_knn_filter_state: the search did not run the filter");
@@ -1231,8 +700,8 @@ int fx_knn_filter_counts(const void* corpus, int dtype, int64_t n, int64_t d, in
                          int metric, int64_t k, int img8, const void* ws, size_t ws_bytes,
                          uint32_t* out_counts, int64_t* out_cap, void* stream) {
   SearchLayout s;
-  int rc = search_layout(corpus, dtype, n, d, nq, metric, k, const_cast<void*>(ws), ws_bytes, &s,
-                         img8 != 0);
+  int rc = search_layout(corpus_of(corpus, dtype, n, d, 0), nq, metric, k, img8 != 0, ws,
+                         ws_bytes, &s);
   if (rc) return rc;
   if (!out_counts || !out_cap) {
     set_error("null pointer argument");
@@ -1257,183 +726,40 @@ int fx_knn_reduce(const void* corpus, int dtype, int64_t n, int64_t d, int64_t r
                   const float* queries, int64_t nq, int metric, int64_t k,
                   const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
                   int64_t* out_row, void* stream) {
-  return reduce_impl(corpus, dtype, n, d, row_base, queries, nq, metric, k, mask, ws, ws_bytes,
-                     out_dist, out_row, stream, false);
+  return reduce_call(corpus_of(corpus, dtype, n, d, row_base), false, queries, nq, metric, k, mask,
+                     ws, ws_bytes, out_dist, out_row, stream);
 }
 
 int fx_knn_reduce_img8(const void* corpus, int dtype, int64_t n, int64_t d, int64_t row_base,
                        const void* image, const float* queries, int64_t nq, int metric, int64_t k,
                        const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
                        int64_t* out_row, void* stream) {
-  return reduce_impl(corpus, dtype, n, d, row_base, queries, nq, metric, k, mask, ws, ws_bytes,
-                     out_dist, out_row, stream, image != nullptr);
+  return reduce_call(corpus_of(corpus, dtype, n, d, row_base), image != nullptr, queries, nq,
+                     metric, k, mask, ws, ws_bytes, out_dist, out_row, stream);
 }
 
 int fx_knn_search(const void* corpus, int dtype, int64_t n, int64_t d, int64_t row_base,
                   const float* queries, int64_t nq, int metric, int64_t k,
                   const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
                   int64_t* out_row, void* stream) {
-  if (!out_dist || !out_row) {
-    set_error("null pointer argument");
-    return FX_EINVAL;
-  }
-  int rc = fx_knn_scan(corpus, dtype, n, d, row_base, queries, nq, metric, k, mask, ws, ws_bytes,
-                       stream);
-  if (rc) return rc;
-  return fx_knn_reduce(corpus, dtype, n, d, row_base, queries, nq, metric, k, mask, ws, ws_bytes,
-                       out_dist, out_row, stream);
+  return search_call(corpus_of(corpus, dtype, n, d, row_base), nullptr, nullptr, false, queries,
+                     nq, metric, k, mask, ws, ws_bytes, out_dist, out_row, stream);
 }
 
 int fx_knn_search_img(const void* corpus, int dtype, int64_t n, int64_t d, int64_t row_base,
                       const void* image, const float* rowinfo, const float* queries, int64_t nq,
                       int metric, int64_t k, const uint32_t* mask, void* ws, size_t ws_bytes,
                       float* out_dist, int64_t* out_row, void* stream) {
-  if (!out_dist || !out_row) {
-    set_error("null pointer argument");
-    return FX_EINVAL;
-  }
-  int rc = fx_knn_scan_img(corpus, dtype, n, d, row_base, image, rowinfo, queries, nq, metric, k,
-                           mask, ws, ws_bytes, stream);
-  if (rc) return rc;
-  return fx_knn_reduce(corpus, dtype, n, d, row_base, queries, nq, metric, k, mask, ws, ws_bytes,
-                       out_dist, out_row, stream);
+  return search_call(corpus_of(corpus, dtype, n, d, row_base), image, rowinfo, false, queries, nq,
+                     metric, k, mask, ws, ws_bytes, out_dist, out_row, stream);
 }
 
 int fx_knn_search_img8(const void* corpus, int dtype, int64_t n, int64_t d, int64_t row_base,
                        const void* image, const float* rowinfo, const float* queries, int64_t nq,
                        int metric, int64_t k, const uint32_t* mask, void* ws, size_t ws_bytes,
                        float* out_dist, int64_t* out_row, void* stream) {
-  if (!out_dist || !out_row) {
-    set_error("null pointer argument");
-    return FX_EINVAL;
-  }
-  int rc = fx_knn_scan_img8(corpus, dtype, n, d, row_base, image, rowinfo, queries, nq, metric, k,
-                            mask, ws, ws_bytes, stream);
-  if (rc) return rc;
-  return reduce_impl(corpus, dtype, n, d, row_base, queries, nq, metric, k, mask, ws, ws_bytes,
-                     out_dist, out_row, stream, image != nullptr);
-}
-
-int fx_knn_search_rows_workspace_bytes(int64_t nrows, int64_t d, int dtype, int64_t nq,
-                                       int64_t k, size_t* out_bytes) {
-  if (!out_bytes) {
-    set_error("null pointer argument");
-    return FX_EINVAL;
-  }
-  int rc = validate(nrows, d, dtype, nq, FX_METRIC_L2);
-  if (rc) return rc;
-  if (k < 1 || k > kLargeMaxK) {
-    set_error("k=%lld outside [1, %lld]", (long long)k, (long long)kLargeMaxK);
-    return FX_EUNSUPPORTED;
-  }
-  SearchLayout s;
-  rc = k > kMaxK ? plan_large_search(nrows, d, dtype, nq, FX_METRIC_L2, true, &s)
-                 : plan_single(nrows, d, dtype, nq, k, FX_METRIC_L2, true, &s);
-  if (rc) return rc;
-  *out_bytes = s.total;
-  return FX_OK;
-}
-
-int fx_knn_search_rows(const void* corpus, int dtype, int64_t n, int64_t d, int64_t row_base,
-                       const int32_t* rows, int64_t nrows, const float* queries, int64_t nq,
-                       int metric, int64_t k, void* ws, size_t ws_bytes, float* out_dist,
-                       int64_t* out_row, void* stream) {
-  int rc = validate(nrows, d, dtype, nq, metric);
-  if (rc) return rc;
-  if (k < 1 || k > kLargeMaxK) {
-    set_error("k=%lld outside [1, %lld]", (long long)k, (long long)kLargeMaxK);
-    return FX_EUNSUPPORTED;
-  }
-  if (!corpus || !ws || !queries || !out_dist || !out_row || (nrows > 0 && !rows)) {
-    set_error("null pointer argument");
-    return FX_EINVAL;
-  }
-  if (row_base < 0 || n < 0 || row_base + n >= 0xffffffffll || n > 0x7fffffffll) {
-    set_error("global rows [%lld, %lld) exceed the 32-bit row space", (long long)row_base,
-              (long long)(row_base + n));
-    return FX_EUNSUPPORTED;
-  }
-  SearchLayout s;
-  const bool aligned = ((uintptr_t)corpus % 16) == 0;
-  rc = k > kMaxK ? plan_large_search(nrows, d, dtype, nq, metric, aligned, &s)
-                 : plan_single(nrows, d, dtype, nq, k, metric, aligned, &s);
-  if (rc) return rc;
-  if (ws_bytes < s.total) {
-    set_error("workspace too small: %zu < %zu", ws_bytes, s.total);
-    return FX_EINVAL;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (s.large) {
-    ScanArgs a = {};
-    a.X = corpus;
-    a.n = nrows;
-    a.d = (int)d;
-    a.row_base = row_base;
-    a.rows = rows;
-    a.rows_per_block = s.scan.rows_per_block;
-    a.cap = s.scan.cap;
-    a.qbytes = s.scan.qbytes;
-    a.q = queries;
-    rc = large_scan(s.scan, a, nq, s.lg, reinterpret_cast<char*>(ws), st);
-    if (rc) return rc;
-    return large_reduce(nrows, nq, k, s.lg, reinterpret_cast<char*>(ws), out_dist, out_row, st);
-  }
-  uint64_t* lists = reinterpret_cast<uint64_t*>(ws);
-  ScanArgs a = {};
-  a.X = corpus;
-  a.n = nrows;
-  a.d = (int)d;
-  a.row_base = row_base;
-  a.rows = rows;
-  a.rows_per_block = s.scan.rows_per_block;
-  a.k = (int)k;
-  a.cap = s.scan.cap;
-  a.qbytes = s.scan.qbytes;
-  a.mode = kModeTopk;
-  for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
-    const int64_t qn = (nq - q0) < 65535 ? (nq - q0) : 65535;
-    a.q = queries + (size_t)q0 * d;
-    a.out_lists = lists + (size_t)q0 * s.scan.nlists * k;
-    rc = launch_scan(s.scan, a, qn, st);
-    if (rc) return rc;
-  }
-  return run_merge(s.merge, lists, nq, k, reinterpret_cast<char*>(ws) + s.lists_bytes, out_dist,
-                   out_row, st);
-}
-
-int fx_knn_distances(const void* corpus, int dtype, int64_t n, int64_t d,
-                     const float* queries, int64_t nq, int metric, const uint32_t* mask,
-                     float* out, void* stream) {
-  int rc = validate(n, d, dtype, nq, metric);
-  if (rc) return rc;
-  if (!corpus || !queries || !out) {
-    set_error("null pointer argument");
-    return FX_EINVAL;
-  }
-  const bool aligned = ((uintptr_t)corpus % 16) == 0;
-  ScanPlan p;
-  rc = plan_scan(n, d, dtype, 1, metric, aligned, &p);
-  if (rc) return rc;
-  ScanArgs a = {};
-  a.X = corpus;
-  a.n = n;
-  a.d = (int)d;
-  a.row_base = 0;
-  a.mask = mask;
-  a.rows_per_block = p.rows_per_block;
-  a.k = 1;
-  a.cap = p.cap;
-  a.qbytes = p.qbytes;
-  a.mode = kModeDist;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
-    const int64_t qn = (nq - q0) < 65535 ? (nq - q0) : 65535;
-    a.q = queries + (size_t)q0 * d;
-    a.out_dist = out + (size_t)q0 * n;
-    rc = launch_scan(p, a, qn, st);
-    if (rc) return rc;
-  }
-  return FX_OK;
+  return search_call(corpus_of(corpus, dtype, n, d, row_base), image, rowinfo, true, queries, nq,
+                     metric, k, mask, ws, ws_bytes, out_dist, out_row, stream);
 }
 
 // merges of lists longer than the fused path's k go through the radix sort

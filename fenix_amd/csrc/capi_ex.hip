@@ -1,96 +1,80 @@
-// Corpus-descriptor entry points (include/fenix_knn.h fx_corpus): every
-// dtype including FX_DTYPE_QU8 (quint8 codes dequantised in the scan's
-// registers, ex/arrow/quint8/quint8.py:81-84), optional row list and mask.
-// Same plans and kernels as fx_knn_search / fx_knn_search_rows /
-// fx_knn_distances; no batched MFMA path here (it reads f32 rows).
+// The exact-scan entry points: a corpus descriptor (include/fenix_knn.h
+// fx_corpus: every dtype including FX_DTYPE_QU8, quint8 codes dequantised in
+// the scan's registers, ex/arrow/quint8/quint8.py:81-84; optional row list
+// and mask), its plain-argument forms fx_knn_search_rows / fx_knn_distances,
+// and several shards under one merge.  Same plans and kernels as fx_knn_search
+// (knn_plan.hip plan_exact); no batched MFMA path here (it reads f32 rows).
 #include <vector>
 
-#include "fx_internal.h"
+#include "fx_plan.h"
 
 namespace fx {
 namespace {
 
-constexpr int64_t kMaxKEx = 1024;  // fused path; larger k: knn_large.hip
+bool rows_fit(int64_t row_base, int64_t n) {
+  if (row_base >= 0 && n >= 0 && row_base + n < 0xffffffffll && n <= 0x7fffffffll) return true;
+  set_error("global rows [%lld, %lld) exceed the 32-bit row space", (long long)row_base,
+            (long long)(row_base + n));
+  return false;
+}
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-int check_corpus(const fx_corpus* c, int64_t nq, int metric) {
+int check_corpus(const fx_corpus* c, int64_t nq, int64_t k, int metric) {
   if (c == nullptr || c->data == nullptr) {
     set_error("null corpus");
     return FX_EINVAL;
   }
-  if (c->n < 1 || c->d < 1 || nq < 1) {
-    set_error("invalid shape n=%lld d=%lld nq=%lld", (long long)c->n, (long long)c->d,
-              (long long)nq);
-    return FX_EINVAL;
-  }
-  if (c->d > (1 << 20)) {
-    set_error("d=%lld too large", (long long)c->d);
-    return FX_EUNSUPPORTED;
-  }
-  if (c->dtype != FX_DTYPE_F32 && c->dtype != FX_DTYPE_F16 && c->dtype != FX_DTYPE_QU8) {
-    set_error("unsupported dtype %d", c->dtype);
-    return FX_EINVAL;
-  }
-  if (metric < FX_METRIC_L2 || metric > FX_METRIC_COS) {
-    set_error("unsupported metric %d", metric);
-    return FX_EINVAL;
-  }
+  int rc = validate(c->n, c->d, c->dtype, nq, k, metric, true);
+  if (rc) return rc;
   if (c->dtype == FX_DTYPE_QU8 && (c->zero_point < 0 || c->zero_point > 255 ||
                                    !(c->scale > 0.f) || c->scale == __builtin_inff())) {
     set_error("quint8 zero_point %d / scale %g out of range", c->zero_point, (double)c->scale);
     return FX_EINVAL;
   }
-  if (c->row_base < 0 || c->row_base + c->n >= 0xffffffffll || c->n > 0x7fffffffll) {
-    set_error("global rows [%lld, %lld) exceed the 32-bit row space", (long long)c->row_base,
-              (long long)(c->row_base + c->n));
-    return FX_EUNSUPPORTED;
-  }
-  return FX_OK;
+  return rows_fit(c->row_base, c->n) ? FX_OK : FX_EUNSUPPORTED;
 }
 
-struct ExPlan {
-  ScanPlan scan;
-  MergePlan merge;
-  size_t lists_bytes, total;
-  bool large = false;
-  LargeLayout lg;
-};
+bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
 
-int plan_ex(const fx_corpus* c, int64_t rows, int64_t nq, int64_t k, int metric, ExPlan* p) {
-  if (k < 1 || k > 0x7fffffffll) {
-    set_error("k=%lld out of range", (long long)k);
-    return FX_EUNSUPPORTED;
+// Exact top-k over the corpus's rows, or over a row list of it (checked
+// arguments): plan, scan, then the merge (k <= kMaxK) or the radix sort
+int exact_search(const fx_corpus& c, const int32_t* rows, int64_t nrows, const float* queries,
+                 int64_t nq, int metric, int64_t k, const uint32_t* mask, void* ws,
+                 size_t ws_bytes, float* out_dist, int64_t* out_row, void* stream) {
+  const int64_t n = rows != nullptr ? nrows : c.n;
+  SearchLayout s;
+  int rc = plan_exact(n, c.d, c.dtype, nq, k, metric, aligned16(c.data), &s);
+  if (rc) return rc;
+  if (ws_bytes < s.total) {
+    set_error("workspace too small: %zu < %zu", ws_bytes, s.total);
+    return FX_EINVAL;
   }
-  const bool aligned = ((uintptr_t)c->data % 16) == 0;
-  if (k > kMaxKEx) {
-    int rc = plan_scan(rows, c->d, c->dtype, 1, metric, aligned, &p->scan);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* w = reinterpret_cast<char*>(ws);
+  ScanArgs a = scan_args(s.scan, c, rows, nrows, mask, s.large ? 1 : k,
+                         s.large ? kModeDist : kModeTopk);
+  a.q = queries;
+  if (s.large) {
+    rc = large_scan(s.scan, a, nq, s.lg, w, st);
     if (rc) return rc;
-    p->large = true;
-    p->lg = plan_large(rows, nq);
-    p->total = p->lg.total;
-    return FX_OK;
+    return large_reduce(n, nq, k, s.lg, w, out_dist, out_row, st);
   }
-  int rc = plan_scan(rows, c->d, c->dtype, k, metric, aligned, &p->scan);
+  a.out_lists = reinterpret_cast<uint64_t*>(ws);
+  rc = launch_scan_queries(s.scan, a, nq, st);
   if (rc) return rc;
-  rc = plan_merge(nq, p->scan.nlists, k, k, &p->merge);
-  if (rc) return rc;
-  p->lists_bytes = align256((size_t)nq * p->scan.nlists * k * 8);
-  p->total = p->lists_bytes + p->merge.ws_bytes;
-  return FX_OK;
+  return run_merge(s.merge, a.out_lists, nq, k, w + s.lists_bytes, out_dist, out_row, st);
 }
 
-ScanArgs base_args(const fx_corpus* c, const ScanPlan& p) {
-  ScanArgs a = {};
-  a.X = c->data;
-  a.d = (int)c->d;
-  a.row_base = c->row_base;
-  a.rows_per_block = p.rows_per_block;
-  a.cap = p.cap;
-  a.qbytes = p.qbytes;
-  a.qscale = c->dtype == FX_DTYPE_QU8 ? c->scale : 1.f;
-  a.qshift = c->dtype == FX_DTYPE_QU8 ? (float)c->zero_point : 0.f;
-  return a;
+// Every distance [nq][c.n] (checked arguments)
+int exact_distances(const fx_corpus& c, const float* queries, int64_t nq, int metric,
+                    const uint32_t* mask, float* out, void* stream) {
+  ScanPlan p;
+  int rc = plan_scan(c.n, c.d, c.dtype, 1, metric, aligned16(c.data), &p);
+  if (rc) return rc;
+  ScanArgs a = scan_args(p, c, nullptr, 0, mask, 1, kModeDist);
+  a.row_base = 0;
+  a.q = queries;
+  a.out_dist = out;
+  return launch_scan_queries(p, a, nq, reinterpret_cast<hipStream_t>(stream));
 }
 
 // fx_knn_search_shards: every shard's scan plan, and where its lists start
@@ -110,12 +94,12 @@ int check_shards(const fx_corpus* s, int ns, int64_t nq, int64_t k, int metric) 
     set_error("fx_knn_search_shards: %d shards (1 .. %d)", ns, kMaxShards);
     return FX_EINVAL;
   }
-  if (k < 1 || k > kMaxKEx) {
-    set_error("fx_knn_search_shards: k=%lld outside [1, %lld]", (long long)k, (long long)kMaxKEx);
+  if (k < 1 || k > kMaxK) {
+    set_error("fx_knn_search_shards: k=%lld outside [1, %lld]", (long long)k, (long long)kMaxK);
     return FX_EUNSUPPORTED;
   }
   for (int i = 0; i < ns; ++i) {
-    int rc = check_corpus(&s[i], nq, metric);
+    int rc = check_corpus(&s[i], nq, k, metric);
     if (rc) return rc;
     if (s[i].d != s[0].d || s[i].dtype != s[0].dtype) {
       set_error("fx_knn_search_shards: shard %d has d=%lld dtype %d, shard 0 d=%lld dtype %d", i,
@@ -131,8 +115,7 @@ int plan_shards(const fx_corpus* s, int ns, int64_t nq, int64_t k, int metric, S
   p->base.resize(ns);
   p->lists = 0;
   for (int i = 0; i < ns; ++i) {
-    const bool aligned = ((uintptr_t)s[i].data % 16) == 0;
-    int rc = plan_scan(s[i].n, s[i].d, s[i].dtype, k, metric, aligned, &p->scan[i]);
+    int rc = plan_scan(s[i].n, s[i].d, s[i].dtype, k, metric, aligned16(s[i].data), &p->scan[i]);
     if (rc) return rc;
     p->base[i] = p->lists;
     p->lists += p->scan[i].nlists;
@@ -151,9 +134,52 @@ using namespace fx;
 
 extern "C" {
 
+int fx_knn_search_rows_workspace_bytes(int64_t nrows, int64_t d, int dtype, int64_t nq,
+                                       int64_t k, size_t* out_bytes) {
+  if (!out_bytes) {
+    set_error("null pointer argument");
+    return FX_EINVAL;
+  }
+  int rc = validate(nrows, d, dtype, nq, k, FX_METRIC_L2, false);
+  if (rc) return rc;
+  SearchLayout s;
+  rc = plan_exact(nrows, d, dtype, nq, k, FX_METRIC_L2, true, &s);
+  if (rc) return rc;
+  *out_bytes = s.total;
+  return FX_OK;
+}
+
+int fx_knn_search_rows(const void* corpus, int dtype, int64_t n, int64_t d, int64_t row_base,
+                       const int32_t* rows, int64_t nrows, const float* queries, int64_t nq,
+                       int metric, int64_t k, void* ws, size_t ws_bytes, float* out_dist,
+                       int64_t* out_row, void* stream) {
+  int rc = validate(nrows, d, dtype, nq, k, metric, false);
+  if (rc) return rc;
+  if (!corpus || !ws || !queries || !out_dist || !out_row || !rows) {
+    set_error("null pointer argument");
+    return FX_EINVAL;
+  }
+  if (!rows_fit(row_base, n)) return FX_EUNSUPPORTED;
+  return exact_search(corpus_of(corpus, dtype, n, d, row_base), rows, nrows, queries, nq, metric,
+                      k, nullptr, ws, ws_bytes, out_dist, out_row, stream);
+}
+
+int fx_knn_distances(const void* corpus, int dtype, int64_t n, int64_t d,
+                     const float* queries, int64_t nq, int metric, const uint32_t* mask,
+                     float* out, void* stream) {
+  int rc = validate(n, d, dtype, nq, 1, metric, false);
+  if (rc) return rc;
+  if (!corpus || !queries || !out) {
+    set_error("null pointer argument");
+    return FX_EINVAL;
+  }
+  return exact_distances(corpus_of(corpus, dtype, n, d, 0), queries, nq, metric, mask, out,
+                         stream);
+}
+
 int fx_knn_search_ex_workspace_bytes(const fx_corpus* c, int64_t nrows, int64_t nq, int64_t k,
                                      size_t* out_bytes) {
-  int rc = check_corpus(c, nq, FX_METRIC_L2);
+  int rc = check_corpus(c, nq, k, FX_METRIC_L2);
   if (rc) return rc;
   if (out_bytes == nullptr) {
     set_error("null pointer argument");
@@ -164,10 +190,10 @@ int fx_knn_search_ex_workspace_bytes(const fx_corpus* c, int64_t nrows, int64_t 
     set_error("empty row list");
     return FX_EINVAL;
   }
-  ExPlan p;
-  rc = plan_ex(c, rows, nq, k, FX_METRIC_L2, &p);
+  SearchLayout s;
+  rc = plan_exact(rows, c->d, c->dtype, nq, k, FX_METRIC_L2, aligned16(c->data), &s);
   if (rc) return rc;
-  *out_bytes = p.total;
+  *out_bytes = s.total;
   return FX_OK;
 }
 
@@ -175,79 +201,29 @@ int fx_knn_search_ex(const fx_corpus* c, const int32_t* rows, int64_t nrows,
                      const float* queries, int64_t nq, int metric, int64_t k,
                      const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
                      int64_t* out_row, void* stream) {
-  int rc = check_corpus(c, nq, metric);
+  int rc = check_corpus(c, nq, k, metric);
   if (rc) return rc;
   if (!queries || !ws || !out_dist || !out_row) {
     set_error("null pointer argument");
     return FX_EINVAL;
   }
-  const int64_t n = rows != nullptr ? nrows : c->n;
-  if (n < 1) {
+  if (rows != nullptr && nrows < 1) {
     set_error("empty row list");
     return FX_EINVAL;
   }
-  ExPlan p;
-  rc = plan_ex(c, n, nq, k, metric, &p);
-  if (rc) return rc;
-  if (ws_bytes < p.total) {
-    set_error("workspace too small: %zu < %zu", ws_bytes, p.total);
-    return FX_EINVAL;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (p.large) {
-    ScanArgs a = base_args(c, p.scan);
-    a.n = n;
-    a.rows = rows;
-    a.mask = mask;
-    a.q = queries;
-    rc = large_scan(p.scan, a, nq, p.lg, reinterpret_cast<char*>(ws), st);
-    if (rc) return rc;
-    return large_reduce(n, nq, k, p.lg, reinterpret_cast<char*>(ws), out_dist, out_row, st);
-  }
-  uint64_t* lists = reinterpret_cast<uint64_t*>(ws);
-  ScanArgs a = base_args(c, p.scan);
-  a.n = n;
-  a.rows = rows;
-  a.mask = mask;
-  a.k = (int)k;
-  a.mode = kModeTopk;
-  for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
-    const int64_t qn = (nq - q0) < 65535 ? (nq - q0) : 65535;
-    a.q = queries + (size_t)q0 * c->d;
-    a.out_lists = lists + (size_t)q0 * p.scan.nlists * k;
-    rc = launch_scan(p.scan, a, qn, st);
-    if (rc) return rc;
-  }
-  return run_merge(p.merge, lists, nq, k, reinterpret_cast<char*>(ws) + p.lists_bytes, out_dist,
-                   out_row, st);
+  return exact_search(*c, rows, nrows, queries, nq, metric, k, mask, ws, ws_bytes, out_dist,
+                      out_row, stream);
 }
 
 int fx_knn_distances_ex(const fx_corpus* c, const float* queries, int64_t nq, int metric,
                         const uint32_t* mask, float* out, void* stream) {
-  int rc = check_corpus(c, nq, metric);
+  int rc = check_corpus(c, nq, 1, metric);
   if (rc) return rc;
   if (!queries || !out) {
     set_error("null pointer argument");
     return FX_EINVAL;
   }
-  ScanPlan p;
-  rc = plan_scan(c->n, c->d, c->dtype, 1, metric, ((uintptr_t)c->data % 16) == 0, &p);
-  if (rc) return rc;
-  ScanArgs a = base_args(c, p);
-  a.n = c->n;
-  a.row_base = 0;
-  a.mask = mask;
-  a.k = 1;
-  a.mode = kModeDist;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
-    const int64_t qn = (nq - q0) < 65535 ? (nq - q0) : 65535;
-    a.q = queries + (size_t)q0 * c->d;
-    a.out_dist = out + (size_t)q0 * c->n;
-    rc = launch_scan(p, a, qn, st);
-    if (rc) return rc;
-  }
-  return FX_OK;
+  return exact_distances(*c, queries, nq, metric, mask, out, stream);
 }
 
 int fx_knn_search_shards_workspace_bytes(const fx_corpus* shards, int nshards, int64_t nq,
@@ -287,22 +263,15 @@ int fx_knn_search_shards(const fx_corpus* shards, int nshards, const float* quer
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   uint64_t* lists = reinterpret_cast<uint64_t*>(ws);
-  const int64_t d = shards[0].d;
   for (int i = 0; i < nshards; ++i) {
-    ScanArgs a = base_args(&shards[i], p.scan[i]);
-    a.n = shards[i].n;
-    a.mask = masks != nullptr ? masks[i] : nullptr;
-    a.k = (int)k;
-    a.mode = kModeTopk;
+    ScanArgs a = scan_args(p.scan[i], shards[i], nullptr, 0, masks != nullptr ? masks[i] : nullptr,
+                           k, kModeTopk);
+    a.q = queries;
+    a.out_lists = lists;
     a.list_stride = p.lists;
     a.list_base = p.base[i];
-    for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
-      const int64_t qn = (nq - q0) < 65535 ? (nq - q0) : 65535;
-      a.q = queries + (size_t)q0 * d;
-      a.out_lists = lists + (size_t)q0 * p.lists * k;
-      rc = launch_scan(p.scan[i], a, qn, st);
-      if (rc) return rc;
-    }
+    rc = launch_scan_queries(p.scan[i], a, nq, st);
+    if (rc) return rc;
   }
   return run_merge(p.merge, lists, nq, k, reinterpret_cast<char*>(ws) + p.lists_bytes, out_dist,
                    out_row, st);

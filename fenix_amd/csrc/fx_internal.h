@@ -16,28 +16,49 @@ constexpr int kCountStride = 32;
 // fits the 160 KB of a CU up to 2 048; also the bound of option "i8_max_k"
 constexpr int kSelectMaxK = 2048;
 
-// Process-wide options (fx_set_option, include/fenix_knn.h); relaxed atomics.
+// Process-wide options (fx_set_option, include/fenix_knn.h); relaxed atomics
+// (fx_runtime.hip).  One line per option: enumerator, name, default; the enum,
+// the names fx_set_option accepts and the defaults all come from this list, in
+// this order (_lib.OPTIONS repeats the names; tests/test_abi.py compares).
+//   filter_image         filter image bits for f32 corpora (engine policy): 8, 16 or 0 (none)
+//   batch_ub_test        sampling phases append by upper bound (0: by lower bound, test switch)
+//   single_query_image   single queries over large f32 corpora through a supplied int8 image
+//   i8_max_k             largest k an int8 filter image serves
+//   img6                 int8 images: resident-query-slice kernel (1: <= 128 queries, 2: all, 0: off)
+//   img8                 int8 images: queries-in-registers kernel for > 128 queries, d <= 768 (0: off)
+//   i8_sample_ratio      int8 images: F1 holds every r1-th tile (filter_phases_i8)
+//   i8_grow_ratio        int8 images: the samples before F1 shrink by r2 each
+//   select_prune         int8 images: 1: selects at k >= 512 prune first; 2: any k; 0: never
+//   scan_stream          plain f32 / f16 scans: 1: streaming kernel, 0: register tiles, -1: by class
+#define FX_OPTIONS(FX_OPTION)                               \
+  FX_OPTION(kOptBatched, "batched", 1)                      \
+  FX_OPTION(kOptBatchMinQ, "batch_min_queries", 2)          \
+  FX_OPTION(kOptBatchCap, "batch_cap", 0)                   \
+  FX_OPTION(kOptBatchRatio, "batch_sample_ratio", 0)        \
+  FX_OPTION(kOptForceFallback, "force_fallback", 0)         \
+  FX_OPTION(kOptScanInterleave, "scan_interleave", -1)      \
+  FX_OPTION(kOptQ8Dma, "q8_dma", 1)                         \
+  FX_OPTION(kOptFilterImage, "filter_image", 8)             \
+  FX_OPTION(kOptBatchUbTest, "batch_ub_test", 1)            \
+  FX_OPTION(kOptSingleImage, "single_query_image", 1)       \
+  FX_OPTION(kOptI8MaxK, "i8_max_k", 1024)                   \
+  FX_OPTION(kOptImg6, "img6", 1)                            \
+  FX_OPTION(kOptImg8, "img8", 1)                            \
+  FX_OPTION(kOptI8SampleRatio, "i8_sample_ratio", 8)        \
+  FX_OPTION(kOptI8GrowRatio, "i8_grow_ratio", 16)           \
+  FX_OPTION(kOptSelectPrune, "select_prune", 1)             \
+  FX_OPTION(kOptScanStream, "scan_stream", -1)
 enum Option : int {
-  kOptBatched,
-  kOptBatchMinQ,
-  kOptBatchCap,
-  kOptBatchRatio,
-  kOptForceFallback,
-  kOptScanInterleave,
-  kOptQ8Dma,
-  kOptFilterImage,  // filter image bits for f32 corpora (engine policy): 8, 16 or 0 (none)
-  kOptBatchUbTest,  // sampling phases append by upper bound (0: by lower bound, test switch)
-  kOptSingleImage,  // single queries over large f32 corpora through a supplied int8 image
-  kOptI8MaxK,       // largest k an int8 filter image serves
-  kOptImg6,         // int8 images: resident-query-slice kernel (1: <= 128 queries, 2: all, 0: off)
-  kOptImg8,         // int8 images: queries-in-registers kernel for > 128 queries, d <= 768 (0: off)
-  kOptI8SampleRatio,  // int8 images: F1 holds every r1-th tile (filter_phases_i8)
-  kOptI8GrowRatio,    // int8 images: the samples before F1 shrink by r2 each
-  kOptSelectPrune,    // int8 images: 1: selects at k >= 512 prune first; 2: any k; 0: never
-  kOptScanStream,     // plain f32 / f16 scans: 1: streaming kernel, 0: register tiles, -1: by class
+#define FX_OPTION_ENUM(id, name, dflt) id,
+  FX_OPTIONS(FX_OPTION_ENUM)
+#undef FX_OPTION_ENUM
   kOptCount
 };
 int64_t option(Option o);
+// fx_set_option / fx_get_option / fx_last_error (unknown name: FX_EINVAL)
+int set_option(const char* name, int64_t value);
+int get_option(const char* name, int64_t* out);
+const char* last_error();
 
 // Diagnostic builds for tools/ (make diag: -DFX_DIAG_BUILD) read a few
 // variant and tuning switches from the environment; the product library
@@ -160,16 +181,19 @@ int launch_exact_kth(const void* X, int dtype, int64_t n, int d, int64_t row_bas
 // run_merge (top-k by key of each query's first count[q] entries of keys
 // [nq][cap]) + launch_exact_kth in one launch, any cap (knn_batch.hip
 // select_kernel, streaming over LDS-sized chunks)
-// prune (these three): scratch of select_prune_bytes(nq, k, cap) or null;
-// a plan that prunes (k ~ 1 000 over a large buffer) first keeps the k
-// smallest of every LDS-sized slice in parallel (select_kernel MODE 3)
+// prune, prune_lists (these three): a plan that prunes (k ~ 1 000 over a
+// large buffer) first keeps the k smallest of every LDS-sized slice in
+// parallel (select_kernel MODE 3).  The plan fixes the slice count once
+// (BatchLayout::prune_lists = select_prune_lists(k, cap), 0 = no prune pass)
+// and reserves select_prune_bytes(nq, k, prune_lists) of scratch for it; the
+// launchers take both as given and read no option.
 int select_prune_lists(int64_t k, int64_t cap);
-size_t select_prune_bytes(int64_t nq, int64_t k, int64_t cap);
+size_t select_prune_bytes(int64_t nq, int64_t k, int prune_lists);
 int launch_exact_threshold(const void* X, int dtype, int64_t n, int d, int64_t row_base,
                            const float* Q, const float* qnorm, int64_t nq, const uint64_t* keys,
                            int64_t cap, uint32_t* count, bool zero_count, int k, int metric,
-                           uint64_t* thr, hipStream_t stream, uint64_t* prune = nullptr,
-                           int64_t* topr = nullptr, const uint64_t* gate_cand = nullptr,
+                           uint64_t* thr, hipStream_t stream, uint64_t* prune, int prune_lists,
+                           int64_t* topr, const uint64_t* gate_cand = nullptr,
                            int64_t gate_num = 0, int64_t gate_den = 1);
 // (gate_cand: launch_overflow_gate(gate_cand, count, thr, nq, cap, gate_num,
 // gate_den) follows on the new thresholds, fused into the select's workgroups
@@ -178,15 +202,15 @@ int launch_exact_threshold(const void* X, int dtype, int64_t n, int d, int64_t r
 // when it has at least k (run_merge's threshold-only level, any cap)
 int launch_sample_threshold(const uint64_t* keys, int64_t nq, int64_t cap, uint32_t* count,
                             bool zero_count, int k, uint64_t* thr, hipStream_t stream,
-                            uint64_t* prune = nullptr);
+                            uint64_t* prune, int prune_lists);
 // the final top-k of each query's first count[q] exact composites of keys
 // [nq][cap], sorted and decoded (run_merge's last level, one workgroup per
 // query, any cap); a query whose count exceeds alt_gate selects from its
 // alt_m entries of alt ([nq][alt_m], the overflow fallback scan's lists)
 int launch_final_select(const uint64_t* keys, int64_t nq, int64_t cap, const uint32_t* count,
                         int k, float* out_dist, int64_t* out_row, const uint64_t* alt,
-                        int64_t alt_m, int64_t alt_gate, hipStream_t stream,
-                        uint64_t* prune = nullptr);
+                        int64_t alt_m, int64_t alt_gate, hipStream_t stream, uint64_t* prune,
+                        int prune_lists);
 
 // Batched filter on the fp16 matrix cores (knn_filter.hip: the entry points
 // and the fp16 error bound; the kernels: filter/*.inc, compiled into the
@@ -280,7 +304,7 @@ int launch_encode(const float* dist, const int64_t* row, int64_t count, uint64_t
 int launch_fill(void* x, int dtype, int64_t n, int64_t d, uint64_t seed, int64_t row_base,
                 int64_t cluster, hipStream_t stream);
 
-// error / device helpers (capi.hip)
+// error / device helpers (fx_runtime.hip)
 void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 int check_launch(const char* what);
 int device_cus(int* out);

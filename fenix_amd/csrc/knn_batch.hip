@@ -22,7 +22,7 @@
 // per-query candidate buffer in HBM (one atomic per append).  Thresholds come
 // from earlier launches of the same kernel over row samples: the k-th
 // composite of ANY subset of rows upper-bounds the global k-th, so filtering
-// with it never drops a true top-k row (capi.hip: batched_search).  The
+// with it never drops a true top-k row (capi.hip: batched_phases).  The
 // buffers are then reduced by the ordinary merge kernels.
 #include "fx_internal.h"
 #include "fx_select.h"
@@ -875,6 +875,8 @@ __global__ void __launch_bounds__(kSelectThreads)
 // The prune pass (select_kernel MODE 3): slices of kSelectEntries, used for
 // k >= kPruneMinK when the buffer holds more than two slices (int8-image
 // plans at k ~ 1 000: ~100 K candidates per query).  k-lists per query, 0 = off.
+// Read by the planner alone (option "select_prune"): the launchers below take
+// the plan's count, which also sized their scratch.
 constexpr int kPruneMinK = 512;
 int select_prune_lists(int64_t k, int64_t cap) {
   const int64_t o = option(kOptSelectPrune);
@@ -882,8 +884,8 @@ int select_prune_lists(int64_t k, int64_t cap) {
   return (int)((cap + kSelectEntries - 1) / kSelectEntries);
 }
 
-size_t select_prune_bytes(int64_t nq, int64_t k, int64_t cap) {
-  return (size_t)nq * (size_t)select_prune_lists(k, cap) * (size_t)k * 8;
+size_t select_prune_bytes(int64_t nq, int64_t k, int prune_lists) {
+  return (size_t)nq * (size_t)prune_lists * (size_t)k * 8;
 }
 
 template <typename T, int MODE>
@@ -932,17 +934,18 @@ static int launch_select_one(const T* X, int64_t n, int d, int64_t row_base, con
 }
 
 // One select (MODE 0/1/2); with a prune scratch (select_prune_bytes, may be
-// null) and a plan that prunes (select_prune_lists), the MODE 3 pass first.
+// null) of pre_p > 0 lists per query (the plan's prune_lists), the MODE 3
+// pass first.
 template <typename T, int MODE>
 static int launch_select_t(const T* X, int64_t n, int d, int64_t row_base, const float* Q,
                            const float* qnorm, int64_t nq, const uint64_t* keys, int64_t cap,
                            uint32_t* count, int zero, int k, int metric, uint64_t* thr,
                            float* out_dist, int64_t* out_row, const uint64_t* alt,
-                           int64_t alt_m, int64_t alt_gate, hipStream_t stream,
-                           uint64_t* pre = nullptr, const uint64_t* gate_cand = nullptr,
+                           int64_t alt_m, int64_t alt_gate, hipStream_t stream, uint64_t* pre,
+                           int pre_p, const uint64_t* gate_cand = nullptr,
                            int64_t gate_num = 0, int64_t gate_den = 1) {
-  const int pre_p = pre != nullptr ? select_prune_lists(k, cap) : 0;
-  if (pre_p == 0) pre = nullptr;
+  if (pre == nullptr) pre_p = 0;
+  if (pre_p <= 0) pre = nullptr;
   if (pre != nullptr) {
     int rc = launch_select_one<T, 3>(X, n, d, row_base, Q, qnorm, nq, keys, cap, count, 0, k,
                                      metric, thr, out_dist, out_row, alt, alt_m, alt_gate, pre,
@@ -957,8 +960,9 @@ static int launch_select_t(const T* X, int64_t n, int d, int64_t row_base, const
 int launch_exact_threshold(const void* X, int dtype, int64_t n, int d, int64_t row_base,
                            const float* Q, const float* qnorm, int64_t nq, const uint64_t* keys,
                            int64_t cap, uint32_t* count, bool zero_count, int k, int metric,
-                           uint64_t* thr, hipStream_t stream, uint64_t* prune, int64_t* topr,
-                           const uint64_t* gate_cand, int64_t gate_num, int64_t gate_den) {
+                           uint64_t* thr, hipStream_t stream, uint64_t* prune, int prune_lists,
+                           int64_t* topr, const uint64_t* gate_cand, int64_t gate_num,
+                           int64_t gate_den) {
   if (k > kSelectMaxK || k > cap) {
     set_error("exact threshold: k %d beyond cap %lld", k, (long long)cap);
     return FX_EUNSUPPORTED;
@@ -968,18 +972,18 @@ int launch_exact_threshold(const void* X, int dtype, int64_t n, int d, int64_t r
               (long long)gate_den, (int)zero_count);
     return FX_EINVAL;
   }
-  if (prune != nullptr && topr != nullptr && select_prune_lists(k, cap) > 0) {
+  if (prune != nullptr && topr != nullptr && prune_lists > 0) {
     // large k: the pruned select writes the k rows, the chip rescores them
     // (one workgroup rescoring 1 000 rows of 3 KB took ~40 us of its time)
     int rc = dtype == FX_DTYPE_F16
                  ? launch_select_t<_Float16, 0>(reinterpret_cast<const _Float16*>(X), n, d,
                                                 row_base, Q, qnorm, nq, keys, cap, count,
                                                 zero_count ? 1 : 0, k, metric, thr, nullptr, topr,
-                                                nullptr, 0, 0, stream, prune)
+                                                nullptr, 0, 0, stream, prune, prune_lists)
                  : launch_select_t<float, 0>(reinterpret_cast<const float*>(X), n, d, row_base, Q,
                                              qnorm, nq, keys, cap, count, zero_count ? 1 : 0, k,
                                              metric, thr, nullptr, topr, nullptr, 0, 0, stream,
-                                             prune);
+                                             prune, prune_lists);
     if (rc) return rc;
     rc = launch_exact_kth(X, dtype, n, d, row_base, Q, qnorm, nq, k, topr, metric, thr, stream);
     if (rc || gate_cand == nullptr) return rc;
@@ -989,28 +993,29 @@ int launch_exact_threshold(const void* X, int dtype, int64_t n, int d, int64_t r
     return launch_select_t<_Float16, 0>(reinterpret_cast<const _Float16*>(X), n, d, row_base, Q,
                                         qnorm, nq, keys, cap, count, zero_count ? 1 : 0, k, metric,
                                         thr, nullptr, nullptr, nullptr, 0, 0, stream, prune,
-                                        gate_cand, gate_num, gate_den);
+                                        prune_lists, gate_cand, gate_num, gate_den);
   return launch_select_t<float, 0>(reinterpret_cast<const float*>(X), n, d, row_base, Q, qnorm, nq,
                                    keys, cap, count, zero_count ? 1 : 0, k, metric, thr, nullptr,
-                                   nullptr, nullptr, 0, 0, stream, prune, gate_cand, gate_num,
-                                   gate_den);
+                                   nullptr, nullptr, 0, 0, stream, prune, prune_lists, gate_cand,
+                                   gate_num, gate_den);
 }
 
 int launch_sample_threshold(const uint64_t* keys, int64_t nq, int64_t cap, uint32_t* count,
                             bool zero_count, int k, uint64_t* thr, hipStream_t stream,
-                            uint64_t* prune) {
+                            uint64_t* prune, int prune_lists) {
   if (k > kSelectMaxK) {
     set_error("sample threshold: k %d too large", k);
     return FX_EUNSUPPORTED;
   }
   return launch_select_t<float, 2>(nullptr, 0, 1, 0, nullptr, nullptr, nq, keys, cap, count,
                                    zero_count ? 1 : 0, k, FX_METRIC_L2, thr, nullptr, nullptr,
-                                   nullptr, 0, 0, stream, prune);
+                                   nullptr, 0, 0, stream, prune, prune_lists);
 }
 
 int launch_final_select(const uint64_t* keys, int64_t nq, int64_t cap, const uint32_t* count,
                         int k, float* out_dist, int64_t* out_row, const uint64_t* alt,
-                        int64_t alt_m, int64_t alt_gate, hipStream_t stream, uint64_t* prune) {
+                        int64_t alt_m, int64_t alt_gate, hipStream_t stream, uint64_t* prune,
+                        int prune_lists) {
   if (k > kSelectMaxK) {
     set_error("final select: k %d too large", k);
     return FX_EUNSUPPORTED;
@@ -1018,7 +1023,8 @@ int launch_final_select(const uint64_t* keys, int64_t nq, int64_t cap, const uin
   // (MODE 1 reads no rows: the keys are exact composites already)
   return launch_select_t<float, 1>(nullptr, 0, 1, 0, nullptr, nullptr, nq, keys, cap,
                                    const_cast<uint32_t*>(count), 0, k, FX_METRIC_L2, nullptr,
-                                   out_dist, out_row, alt, alt_m, alt_gate, stream, prune);
+                                   out_dist, out_row, alt, alt_m, alt_gate, stream, prune,
+                                   prune_lists);
 }
 
 }  // namespace fx

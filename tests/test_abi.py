@@ -47,6 +47,14 @@ def test_version_and_limits():
 
 
 def test_options_round_trip_and_unknown_names():
+    # the library's one option table (csrc/fx_internal.h FX_OPTIONS): the
+    # names it accepts, in order, are _lib.OPTIONS
+    table = open(os.path.join(ROOT, "fenix_amd", "csrc", "fx_internal.h")).read()
+    rows = re.findall(r'^\s*FX_OPTION\((kOpt\w+), "(\w+)", (-?\d+)\)', table, re.M)
+    assert tuple(name for _, name, _ in rows) == _lib.OPTIONS
+    assert len({enum for enum, _, _ in rows}) == len(rows)
+    for _, name, default in rows:
+        assert _lib.get_option(name) == int(default)
     for name in _lib.OPTIONS:
         old = _lib.get_option(name)
         with _lib.options(**{name: old + 3}):

@@ -7,7 +7,7 @@ samples are equidistributed over the corpus whatever its order.  Every search
 must equal the exact f32 scan bit for bit, and, on these corpora, no query may
 overflow the candidate buffer (which would send it to the exact scan: correct,
 but 1.3x slower than the scan alone).  The shard is >= 4 GiB, so single
-queries take the image (capi.hip use_batched)."""
+queries take the image (knn_plan.hip use_batched)."""
 
 from __future__ import annotations
 

@@ -303,6 +303,47 @@ def test_distances_kernel(eng, metric):
     assert np.isnan(got[:, ~mask]).all()
 
 
+# A launch grid holds 65 535 queries: the exact-scan driver
+# (launch_scan_queries) splits a larger call and offsets queries and outputs
+# per chunk.  65 537 queries put one query alone into a second launch.
+_SPLIT_NQ = 65_537
+_SPLIT_PROBES = [0, 65_534, 65_535, 65_536]
+
+
+def test_query_grid_split(eng):
+    """One fx_knn_search over 65 537 queries == the two calls over queries
+    [0, 40 000) and [40 000, 65 537), bit for bit; the queries on both sides
+    of the split against the float64 oracle."""
+    n, d, k = 300, 8, 3
+    x = gpu_fill(eng, n, d, seed=16)
+    xh = O.fill_normal(n, d, 16)
+    q = O.fill_normal(_SPLIT_NQ, d, 17)
+    with _lib.options(batched=0):
+        gd, gr = gpu_search(eng, x, q, "l2", k)
+        halves = [gpu_search(eng, x, q[a:b], "l2", k) for a, b in ((0, 40_000), (40_000, _SPLIT_NQ))]
+    np.testing.assert_array_equal(gr, np.concatenate([h[1] for h in halves]))
+    np.testing.assert_array_equal(gd.view(np.uint32),
+                                  np.concatenate([h[0] for h in halves]).view(np.uint32))
+    od, orow = O.knn(xh, q[_SPLIT_PROBES], "l2", k)
+    check_topk(gd[_SPLIT_PROBES], gr[_SPLIT_PROBES], od, orow, xh, q[_SPLIT_PROBES], "l2")
+
+
+def test_query_grid_split_distances(eng):
+    """The same split for fx_knn_distances: one call over 65 537 queries ==
+    the two half calls bit for bit, and the rows on both sides of the split
+    within test_distances_kernel's tolerance of the float64 distances."""
+    n, d = 64, 8
+    x = gpu_fill(eng, n, d, seed=18)
+    xh = O.fill_normal(n, d, 18)
+    q = torch.from_numpy(O.fill_normal(_SPLIT_NQ, d, 19))
+    got = eng.distances(Shard(x, 0), q, _lib.METRIC_L2).cpu().numpy()
+    halves = [eng.distances(Shard(x, 0), q[a:b], _lib.METRIC_L2).cpu().numpy()
+              for a, b in ((0, 40_000), (40_000, _SPLIT_NQ))]
+    np.testing.assert_array_equal(got.view(np.uint32), np.concatenate(halves).view(np.uint32))
+    ref = O.distance_f64(xh, q.numpy()[_SPLIT_PROBES], "l2")
+    assert (np.abs(got[_SPLIT_PROBES] - ref) <= 1e-5 * np.maximum(np.abs(ref), 10.0)).all()
+
+
 def test_topk_merge(eng):
     """fx_topk_merge == oracle top-k of the union (the multi-GPU final merge)."""
     rs = np.random.RandomState(2)
