@@ -124,6 +124,9 @@ static int filter_phases(const BatchLayout& b, const void* X, int dtype, const v
     a.diag = diag_env("FX_FILTER_DIAG", 0);
     rc = launch_filter(a, metric, st);
     if (rc) return rc;
+    // option "filter_hold" (test switch): the last pass's bounds, counts and
+    // the threshold it tested against stay in the workspace
+    if (last && option(kOptFilterHold) != 0) return FX_OK;
     // the k-th upper bound of this phase's candidates: next threshold
     rc = run_merge(b.merge, last ? cand_ub : cand, nq, k, w + b.off_merge, nullptr, nullptr, st,
                    thr, nullptr, 0, count, !last);
@@ -234,8 +237,12 @@ static int filter_phases_i8(const BatchLayout& b, const void* X, int dtype, cons
   f1.cand_ub = cand_ub;
   rc = launch_filter(f1, metric, st);
   if (rc) return rc;
+  // option "filter_hold" (test switch): return after the last filter pass, its
+  // bounds, counts and the threshold it tested against left in the workspace
+  const bool hold = option(kOptFilterHold) != 0;
   if (m >= 2) {
     const int64_t t1 = b.num[m - 2], t2 = b.tiles - t1;
+    if (hold && t2 <= 0) return FX_OK;
     // F1's threshold, then (t2 > 0) the overflow gate on it (launch_overflow_gate's
     // prediction, run by the select's own workgroups)
     rc = t2 > 0 ? exact_threshold(cand_ub, false, cand, t2, t1) : exact_threshold(cand_ub, false);
@@ -251,6 +258,7 @@ static int filter_phases_i8(const BatchLayout& b, const void* X, int dtype, cons
       if (rc) return rc;
     }
   }
+  if (hold) return FX_OK;
   // the final threshold only pays for itself on a batch: one or two queries
   // rescore every candidate under F1's threshold instead (a few thousand 3 KB
   // rows, ~3-6 us spread over the chip, against a ~25 us one-workgroup select)

@@ -98,7 +98,7 @@ __device__ __forceinline__ void i3_epilogue(const f32x16 (&acc)[kI2QT], const fl
     const float2 ab = qab[u * 32 + l32];
     const f32x2 na = {-ab.x, -ab.x}, nb = {-ab.y, -ab.y};
     // fail bit j = sign of RN(RN(x_j - a rv_j) - b): set exactly when x_j -
-    // a rv_j rounds below b (NaN passes); bit j enters last-in at bit 0
+    // a rv_j rounds below b; bit j enters last-in at bit 0
     uint32_t fail = 0u;
 #pragma unroll
     for (int i = 7; i >= 0; --i) {
@@ -109,7 +109,10 @@ __device__ __forceinline__ void i3_epilogue(const f32x16 (&acc)[kI2QT], const fl
       fail = __builtin_amdgcn_alignbit(fail, __float_as_uint(dd[1]), 31);
       fail = __builtin_amdgcn_alignbit(fail, __float_as_uint(dd[0]), 31);
     }
-    pm[u] = (diag & 1) ? 0u : (~fail | fmask) & ~smask & 0xffffu;
+    // (b = -inf: no threshold yet or a forced query, every row passes whatever
+    // the sign of a NaN product, filter_epilogue)
+    const uint32_t qall = ab.y == -__builtin_inff() ? ~0u : 0u;
+    pm[u] = (diag & 1) ? 0u : (~fail | fmask | qall) & ~smask & 0xffffu;
     if (q0 + u * 32 + l32 >= a.nq) pm[u] = 0u;
   }
   uint32_t any = 0u;

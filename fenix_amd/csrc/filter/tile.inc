@@ -225,7 +225,11 @@ __device__ __forceinline__ void filter_epilogue(const f32x16 (&acc)[RT][QT], con
         const float t = fmaf(ab.x, ri[roff(j)], ab.y);
         fail = __builtin_amdgcn_alignbit(fail, __float_as_uint(acc[j >> 4][u][j & 15] - t), 31);
       }
-      pm[u] = (diag & 1) ? 0u : ((~fail | fmask) & ~smask & kAll);
+      // (b = -inf: no threshold yet or a forced query, every row passes -- said
+      // here, not left to the sign of acc - t: a non-finite query's products
+      // are NaN of either sign)
+      const uint32_t qall = ab.y == -__builtin_inff() ? ~0u : 0u;
+      pm[u] = (diag & 1) ? 0u : ((~fail | fmask | qall) & ~smask & kAll);
       if (q0 + qg * QT * 32 + u * 32 + l32 >= a.nq) pm[u] = 0u;
     }
     uint32_t any = 0u;
@@ -334,7 +338,11 @@ __device__ __forceinline__ void filter_epilogue_seg(const f32x16 (&acc)[RT][QT],
         const float t = fmaf(ab.x, ri[roff(j)], ab.y);
         fail = __builtin_amdgcn_alignbit(fail, __float_as_uint(acc[j >> 4][u][j & 15] - t), 31);
       }
-      pm[u] = (diag & 1) ? 0u : ((~fail | fmask) & ~smask & kAll);
+      // (b = -inf: no threshold yet or a forced query, every row passes -- said
+      // here, not left to the sign of acc - t: a non-finite query's products
+      // are NaN of either sign)
+      const uint32_t qall = ab.y == -__builtin_inff() ? ~0u : 0u;
+      pm[u] = (diag & 1) ? 0u : ((~fail | fmask | qall) & ~smask & kAll);
       if (q0 + qg * QT * 32 + u * 32 + l32 >= a.nq) pm[u] = 0u;
     }
     uint32_t any = 0u;

@@ -30,6 +30,8 @@ constexpr int kSelectMaxK = 2048;
 //   i8_grow_ratio        int8 images: the samples before F1 shrink by r2 each
 //   select_prune         int8 images: 1: selects at k >= 512 prune first; 2: any k; 0: never
 //   scan_stream          plain f32 / f16 scans: 1: streaming kernel, 0: register tiles, -1: by class
+//   filter_hold          1: the filter phases stop after their last filter pass, the bounds left
+//                        in the workspace for fx_knn_filter_state (test switch; no reduce follows)
 #define FX_OPTIONS(FX_OPTION)                               \
   FX_OPTION(kOptBatched, "batched", 1)                      \
   FX_OPTION(kOptBatchMinQ, "batch_min_queries", 2)          \
@@ -47,7 +49,8 @@ constexpr int kSelectMaxK = 2048;
   FX_OPTION(kOptI8SampleRatio, "i8_sample_ratio", 8)        \
   FX_OPTION(kOptI8GrowRatio, "i8_grow_ratio", 16)           \
   FX_OPTION(kOptSelectPrune, "select_prune", 1)             \
-  FX_OPTION(kOptScanStream, "scan_stream", -1)
+  FX_OPTION(kOptScanStream, "scan_stream", -1)             \
+  FX_OPTION(kOptFilterHold, "filter_hold", 0)
 enum Option : int {
 #define FX_OPTION_ENUM(id, name, dflt) id,
   FX_OPTIONS(FX_OPTION_ENUM)

@@ -640,6 +640,44 @@ class Engine:
             return None, -1
         return out.cpu().numpy().view(np.uint32), int(cap.value)
 
+    def filter_state(self, shard: Shard, nq: int, metric: int, k: int, state: "ScanState",
+                     cap: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """fx_knn_filter_state after ``scan``: (thr [nq], cand [nq, cap], cand_ub
+        [nq, cap]) uint64 composites (key << 32 | global row) on the host;
+        ``cap`` from ``filter_counts``.  After a normal scan ``cand`` holds the
+        rescored candidates' exact keys (kEmpty: dropped) and ``thr`` the final
+        threshold; the bounds themselves are there only under the option
+        "filter_hold" (``filter_bounds``).  Synchronises (tests, tools)."""
+        thr = torch.empty(nq, dtype=torch.int64, device=self.device)
+        cand = torch.empty((nq, cap), dtype=torch.int64, device=self.device)
+        cub = torch.empty((nq, cap), dtype=torch.int64, device=self.device)
+        _lib.check(_lib.load().fx_knn_filter_state(
+            _ptr(shard.data), shard.dtype_id, shard.n, shard.d, nq, metric, k,
+            1 if (state.bits == 8 and state.image is not None) else 0, _ptr(state.ws),
+            state.ws.numel(), _ptr(thr), _ptr(cand), _ptr(cub), self._stream()))
+        return tuple(t.cpu().numpy().view(np.uint64) for t in (thr, cand, cub))
+
+    def filter_bounds(self, shard: Shard, queries: torch.Tensor, metric: int, k: int,
+                      mask: Optional[torch.Tensor] = None) -> Optional[dict]:
+        """The batched filter's own output for one search: ``scan`` under the
+        option "filter_hold" (the phases stop after their last filter pass; no
+        ``reduce`` follows), read back to the host.  Per query q, over slots
+        i < min(count[q], cap): ``cand[q, i]`` the lower-bound composite and
+        ``cand_ub[q, i]`` the upper-bound composite of the same row; ``thr[q]``
+        the threshold the last pass tested against (all ones: none);
+        ``count[q]`` > ``cap``: overflowed, or marked by the overflow gate.
+        ``bits``: the filter image the scan read (8, 16 or 0).  None when the
+        search does not run the filter.  Synchronises (tests, tools)."""
+        nq = queries.shape[0]
+        with _lib.options(filter_hold=1):
+            st = self.scan(shard, queries, metric, k, mask)
+            counts, cap = self.filter_counts(shard, nq, metric, k, st)
+            if counts is None:
+                return None
+            thr, cand, cub = self.filter_state(shard, nq, metric, k, st, cap)
+        return {"count": counts, "cap": cap, "thr": thr, "cand": cand, "cand_ub": cub,
+                "bits": st.bits}
+
     def merge(self, dist: torch.Tensor, row: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """fx_topk_merge of [nq, parts, kin] sorted lists -> [nq, k]."""
         nq, parts, kin = dist.shape

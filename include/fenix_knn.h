@@ -114,6 +114,10 @@ int fx_device_count(int* out);
  *   "scan_stream"        -1  plain f32 / f16 scans of rows that fill their slots:
  *                            1: streaming kernel (register ring, counted waits);
  *                            0: register tiles; -1: by (dtype, row length) class
+ *   "filter_hold"         0  1: a filter scan (fx_knn_scan*) returns after its last
+ *                            filter pass: fx_knn_filter_state then reads the
+ *                            pairs' lower / upper bounds and the threshold that
+ *                            pass tested against; no reduce may follow (test switch)
  * fx_set_option: FX_EINVAL for an unknown name.  Options are read when a call
  * plans its launches; set them while no search is in flight.
  */
@@ -258,8 +262,12 @@ int fx_knn_filter_counts(const void* corpus, int dtype, int64_t n, int64_t d, in
                          int metric, int64_t k, int img8, const void* ws, size_t ws_bytes,
                          uint32_t* out_counts, int64_t* out_cap, void* stream);
 /* The same search's thresholds (device uint64 [nq] composites) and candidate
- * buffers (device uint64 [nq][cap]: lower-bound / exact composites, upper-
- * bound composites; each nullable).  For tests and tools. */
+ * buffers (device uint64 [nq][cap], each nullable; slots below min(count, cap)
+ * are written).  After a normal scan out_cand holds the rescored candidates'
+ * exact composites (all ones: dropped unread) and out_thr the final threshold;
+ * the filter's lower-bound composites are there only under option
+ * "filter_hold".  out_cand_ub: the upper-bound composites, the same rows in
+ * the same slots.  For tests and tools. */
 int fx_knn_filter_state(const void* corpus, int dtype, int64_t n, int64_t d, int64_t nq,
                         int metric, int64_t k, int img8, const void* ws, size_t ws_bytes,
                         uint64_t* out_thr, uint64_t* out_cand, uint64_t* out_cand_ub,

@@ -23,6 +23,42 @@ DIST_RTOL = 1e-5
 NEAR_RTOL = 2e-6
 
 
+KEY_NAN = 0xFFFFFFFF  # order_key of every NaN; the all-ones composite is the empty slot
+EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
+
+
+def order_key(f) -> np.ndarray:
+    """fx_common.h order_key on float32 values: uint32 keys whose unsigned
+    order is the distance order (-0 -> +0, every NaN -> 0xFFFFFFFF, last)."""
+    u = np.ascontiguousarray(f, dtype=np.float32).view(np.uint32)
+    mag = u & np.uint32(0x7FFFFFFF)
+    u = np.where(mag == 0, np.uint32(0), u)
+    key = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+    return np.where(mag > np.uint32(0x7F800000), np.uint32(KEY_NAN), key).astype(np.uint32)
+
+
+def key_float(k) -> np.ndarray:
+    """fx_common.h key_float, the inverse of ``order_key``: float32 values of
+    uint32 keys (0xFFFFFFFF -> the quiet NaN 0x7FC00000)."""
+    k = np.ascontiguousarray(k, dtype=np.uint32)
+    bits = np.where(k & np.uint32(0x80000000), k & np.uint32(0x7FFFFFFF), ~k)
+    bits = np.where(k == np.uint32(KEY_NAN), np.uint32(0x7FC00000), bits)
+    return bits.astype(np.uint32).view(np.float32)
+
+
+def make_comp(dist, row) -> np.ndarray:
+    """fx_common.h make_comp: (order_key(dist) << 32) | global row, uint64."""
+    return (order_key(dist).astype(np.uint64) << np.uint64(32)) | np.asarray(row, dtype=np.uint64)
+
+
+def comp_key(c) -> np.ndarray:
+    return (np.asarray(c, dtype=np.uint64) >> np.uint64(32)).astype(np.uint32)
+
+
+def comp_row(c) -> np.ndarray:
+    return (np.asarray(c, dtype=np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.int64)
+
+
 def scale_of(x: np.ndarray, q: np.ndarray, metric: str) -> np.ndarray:
     xn = float(np.sqrt((np.asarray(x, dtype=np.float64) ** 2).sum(axis=1)).max()) if len(x) else 0.0
     qn = np.sqrt((np.asarray(q, dtype=np.float64) ** 2).sum(axis=1))

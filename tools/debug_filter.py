@@ -1,8 +1,8 @@
 """Debug a filter-image search against the exact scan: which true top-k rows
-are missing from the final candidates, with their bounds.
+are missing from the final candidates, with their bounds (the filter's own
+[lb, ub], held before the rescoring: Engine.filter_bounds).
     python tools/debug_filter.py [--metric l2] [--n 20000] [--d 64] [--nq 16] [--k 25] [--extreme]"""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -13,12 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fenix_amd import _lib  # noqa: E402
 from fenix_amd.engine import Engine, Shard  # noqa: E402
 from oracle import oracle as O  # noqa: E402
-
-
-def key_float(k):
-    k = np.asarray(k, dtype=np.uint32)
-    bits = np.where(k & 0x80000000, k & 0x7fffffff, ~k)
-    return bits.astype(np.uint32).view(np.float32)
+from tests.parity import key_float  # noqa: E402
 
 
 p = argparse.ArgumentParser()
@@ -51,25 +46,20 @@ x = torch.from_numpy(xh).to(eng.device)
 q = torch.from_numpy(qh).to(eng.device)
 m = _lib.METRICS[a.metric]
 shard = Shard(x, 0)
+# the bounds as the last filter pass left them (a normal scan's `cand` holds
+# the rescored exact keys, or the empty key, by the time it returns)
+held = eng.filter_bounds(shard, q, m, a.k)
+if held is None:
+    sys.exit("this search does not run the filter")
+counts, cap, thr, cand, cub = (held[f] for f in ("count", "cap", "thr", "cand", "cand_ub"))
 st = eng.scan(shard, q, m, a.k)
-counts, cap = eng.filter_counts(shard, a.nq, m, a.k, st)
-thr = torch.empty(a.nq, dtype=torch.int64, device=eng.device)
-cand = torch.empty((a.nq, cap), dtype=torch.int64, device=eng.device)
-cub = torch.empty((a.nq, cap), dtype=torch.int64, device=eng.device)
-_lib.check(_lib.load().fx_knn_filter_state(x.data_ptr(), 0, a.n, a.d, a.nq, m, a.k, 1,
-                                            st.ws.data_ptr(), st.ws.numel(), thr.data_ptr(),
-                                            cand.data_ptr(), cub.data_ptr(),
-                                            torch.cuda.current_stream().cuda_stream))
 od = torch.empty((a.nq, a.k), dtype=torch.float32, device=eng.device)
 orow = torch.empty((a.nq, a.k), dtype=torch.int64, device=eng.device)
 eng.reduce(shard, q, m, a.k, st, od, orow)
 torch.cuda.synchronize()
 with _lib.options(batched=0):
     sd, sr = eng.search([shard], q, m, a.k)
-thr = thr.cpu().numpy().view(np.uint64)
-cand = cand.cpu().numpy().view(np.uint64)
-cub = cub.cpu().numpy().view(np.uint64)
-print("cap", cap, "image", st.bits, "counts", counts.tolist())
+print("cap", cap, "image", held["bits"], "counts", counts.tolist())
 fr, sr = orow.cpu().numpy(), sr.cpu().numpy()
 for i in range(a.nq):
     c = min(int(counts[i]), cap)
