@@ -23,7 +23,7 @@ LIB_PATH = os.environ.get("FENIX_AMD_LIB") or os.path.join(HERE, "lib", "libfeni
 
 DTYPE_F32 = 0
 DTYPE_F16 = 1
-DTYPE_QU8 = 2  # quint8 codes (fx_knn_*_ex entry points)
+DTYPE_QU8 = 2  # quint8 codes (the entry points that take a Corpus)
 METRIC_L2 = 0
 METRIC_IP = 1
 METRIC_COS = 2
@@ -83,6 +83,10 @@ SYMBOLS = (
     "fx_knn_search_shards_workspace_bytes",
     "fx_knn_search_shards",
     "fx_knn_distances_ex",
+    "fx_filter_image8_ex",
+    "fx_knn_scan_img8_ex",
+    "fx_knn_reduce_img8_ex",
+    "fx_knn_search_img8_ex",
     "fx_comm_init_all",
     "fx_comm_destroy",
     "fx_allgather_topk",
@@ -97,7 +101,7 @@ SYMBOLS = (
 OPTIONS = ("batched", "batch_min_queries", "batch_cap", "batch_sample_ratio", "force_fallback",
            "scan_interleave", "q8_dma", "filter_image", "batch_ub_test", "single_query_image",
            "i8_max_k", "img6", "img8", "i8_sample_ratio", "i8_grow_ratio", "select_prune",
-           "scan_stream", "filter_hold")
+           "scan_stream", "filter_hold", "qu8_batch_min_work")
 
 _lock = threading.Lock()
 _lib = None
@@ -232,6 +236,14 @@ def load() -> ctypes.CDLL:
         L.fx_knn_search_shards.restype = ci
         L.fx_knn_distances_ex.argtypes = [pc_, vp, i64, ci, vp, vp, vp]
         L.fx_knn_distances_ex.restype = ci
+        L.fx_filter_image8_ex.argtypes = [pc_, vp, vp, vp]
+        L.fx_filter_image8_ex.restype = ci
+        L.fx_knn_scan_img8_ex.argtypes = [pc_, vp, vp, vp, i64, ci, i64, vp, vp, sz, vp]
+        L.fx_knn_scan_img8_ex.restype = ci
+        L.fx_knn_reduce_img8_ex.argtypes = [pc_, vp, vp, i64, ci, i64, vp, vp, sz, vp, vp, vp]
+        L.fx_knn_reduce_img8_ex.restype = ci
+        L.fx_knn_search_img8_ex.argtypes = [pc_, vp, vp, vp, i64, ci, i64, vp, vp, sz, vp, vp, vp]
+        L.fx_knn_search_img8_ex.restype = ci
         L.fx_comm_init_all.argtypes = [ci, ctypes.POINTER(ci), ctypes.POINTER(vp)]
         L.fx_comm_init_all.restype = ci
         L.fx_comm_destroy.argtypes = [vp]
@@ -303,7 +315,8 @@ def _current_device() -> int:
 
 def filter_image_used(n: int, d: int, dtype: int, nq: int, k: int, metric: int) -> bool:
     """True when a search of this shape runs the batched filter over f32 rows,
-    which then streams an fp16 filter image if one is given (fx_filter_image)."""
+    which then streams an fp16 filter image if one is given (fx_filter_image);
+    for quint8 codes, when a batch of this shape goes through an int8 image."""
     def compute() -> bool:
         out = ctypes.c_int(0)
         check(load().fx_filter_image_used(n, d, dtype, nq, k, metric, ctypes.byref(out)))

@@ -161,22 +161,37 @@ static int filter_phases(const BatchLayout& b, const void* X, int dtype, const v
 //     threshold (batches of more than kI8RescoreAllMaxQ queries; smaller ones
 //     keep F1's), and the candidates whose lower bound reaches it are
 //     rescored exactly (launch_rescore), fx_knn_reduce selects the top k.
+// quint8 codes (dtype FX_DTYPE_QU8, z their scale and zero point; the image
+// is image8_qu8_kernel's): the exact distances repeat the quint8 scan, whose
+// L2 form reads q' = zp + q / scale.  q' is computed once into the workspace
+// (launch_qu8_query); the rescoring reads it, and the filter bounds the scan's
+// effective query scale * (q' - zp) (launch_qprep8; the derivation is beside
+// image8_qu8_kernel, knn_filter.hip).  IP and cosine take the queries as they are.
 static constexpr int64_t kI8RescoreAllMaxQ = 2;
 
 static int filter_phases_i8(const BatchLayout& b, const void* X, int dtype, const void* image,
                             const float* rowinfo, int64_t n, int64_t d, int64_t row_base,
                             const float* Q, int64_t nq, int metric, int64_t k,
-                            const uint32_t* mask, char* w, hipStream_t st) {
+                            const uint32_t* mask, char* w, hipStream_t st, Quant z) {
   float* qnorm = reinterpret_cast<float*>(w + b.off_qnorm);
   uint64_t* thr = reinterpret_cast<uint64_t*>(w + b.off_thr);
   uint32_t* count = reinterpret_cast<uint32_t*>(w + b.off_count);
   uint64_t* cand = reinterpret_cast<uint64_t*>(w + b.off_cand);
   uint64_t* cand_ub = reinterpret_cast<uint64_t*>(w + b.off_cand_ub);
   const int64_t nq_pad8 = (nq + 255) / 256 * 256;
+  int rc;
+  const bool qu8_l2 = dtype == FX_DTYPE_QU8 && metric == FX_METRIC_L2;
+  if (qu8_l2) {  // from here on Q is the quint8 scan's q' (L2 needs no |q|)
+    float* qt = reinterpret_cast<float*>(w + b.off_qt);
+    rc = launch_qu8_query(Q, nq, (int)d, z, qt, st);
+    if (rc) return rc;
+    Q = qt;
+  }
   // (the query prep also empties thr and zeroes the counts)
-  int rc = launch_qprep8(Q, nq, nq_pad8, (int)d, b.dq, metric,
-                         reinterpret_cast<int8_t*>(w + b.off_qh),
-                         reinterpret_cast<float*>(w + b.off_qinfo), st, thr, count);
+  rc = launch_qprep8(Q, nq, nq_pad8, (int)d, b.dq, metric,
+                     reinterpret_cast<int8_t*>(w + b.off_qh),
+                     reinterpret_cast<float*>(w + b.off_qinfo), st, thr, count,
+                     qu8_l2 ? &z : nullptr);
   if (rc) return rc;
   if (metric == FX_METRIC_COS) {  // the scan's max(|q|, 1e-12) for the exact distances
     rc = launch_qnorm(Q, nq, (int)d, qnorm, st, 0);
@@ -216,7 +231,7 @@ static int filter_phases_i8(const BatchLayout& b, const void* X, int dtype, cons
                              int64_t gate_num = 0, int64_t gate_den = 1) {
     return launch_exact_threshold(X, dtype, n, (int)d, row_base, Q, qnorm, nq, keys, b.cap, count,
                                   zero, (int)k, metric, thr, st, prune, b.prune_lists, topr, gate,
-                                  gate_num, gate_den);
+                                  gate_num, gate_den, z);
   };
   const int m = b.nphases;
   for (int ph = 0; ph + 2 < m; ++ph) {  // sampling phases: thresholds only
@@ -267,7 +282,7 @@ static int filter_phases_i8(const BatchLayout& b, const void* X, int dtype, cons
     if (rc) return rc;
   }
   return launch_rescore(X, dtype, n, (int)d, row_base, Q, qnorm, nq, count, cand, (int)b.cap,
-                        metric, thr, st);
+                        metric, thr, st, z);
 }
 
 #ifdef FX_DIAG_BUILD
@@ -368,7 +383,7 @@ int fx_knn_workspace_bytes_img8(int64_t n, int64_t d, int dtype, int64_t nq, int
     set_error("out_bytes is null");
     return FX_EINVAL;
   }
-  int rc = validate(n, d, dtype, nq, k, FX_METRIC_L2, false);
+  int rc = validate(n, d, dtype, nq, k, FX_METRIC_L2, true);
   if (rc) return rc;
   size_t best = 0;
   for (int metric = 0; metric < 3; ++metric) {
@@ -391,10 +406,14 @@ int fx_knn_workspace_bytes_img8(int64_t n, int64_t d, int dtype, int64_t nq, int
 
 // One call's plan: arguments checked (shape, k, then null pointers), planned
 // once from the options as they are now, and held against the workspace the
-// call brought.  img8: the call supplies an int8 filter image.
+// call brought.  img8: the call supplies an int8 filter image.  qu8: the
+// entry point takes quint8 codes (a descriptor with their scale and zero
+// point, or a call that only reads the plan).
 static int search_layout(const fx_corpus& c, int64_t nq, int metric, int64_t k, bool img8,
-                         const void* ws, size_t ws_bytes, SearchLayout* s) {
-  int rc = validate(c.n, c.d, c.dtype, nq, k, metric, false);
+                         const void* ws, size_t ws_bytes, SearchLayout* s, bool qu8 = false) {
+  int rc = validate(c.n, c.d, c.dtype, nq, k, metric, qu8);
+  if (rc) return rc;
+  rc = validate_quant(c);
   if (rc) return rc;
   if (!c.data || !ws) {
     set_error("null pointer argument");
@@ -439,7 +458,12 @@ static int scan_impl(const SearchLayout& s, const fx_corpus& c, const void* imag
       }
       if (img && img8)
         return filter_phases_i8(s.batch, c.data, c.dtype, image, rowinfo, c.n, c.d, c.row_base,
-                                queries, nq, metric, k, mask, w, st);
+                                queries, nq, metric, k, mask, w, st,
+                                Quant{c.scale, (float)c.zero_point});
+      if (c.dtype == FX_DTYPE_QU8) {  // (unreachable: quint8 batches are planned on an image)
+        set_error("quint8 batch without an int8 filter image");
+        return FX_EINVAL;
+      }
       return filter_phases(s.batch, c.data, c.dtype, img ? image : nullptr, rowinfo, c.n, c.d,
                            c.row_base, queries, nq, metric, k, mask, w, st);
     }
@@ -462,9 +486,10 @@ static int scan_impl(const SearchLayout& s, const fx_corpus& c, const void* imag
 // The scan half of a search call: plan, then run (fx_knn_scan*)
 static int scan_call(const fx_corpus& c, const void* image, const float* rowinfo, bool img8,
                      const float* queries, int64_t nq, int metric, int64_t k,
-                     const uint32_t* mask, void* ws, size_t ws_bytes, void* stream) {
+                     const uint32_t* mask, void* ws, size_t ws_bytes, void* stream,
+                     bool qu8 = false) {
   SearchLayout s;
-  int rc = search_layout(c, nq, metric, k, img8 && image != nullptr, ws, ws_bytes, &s);
+  int rc = search_layout(c, nq, metric, k, img8 && image != nullptr, ws, ws_bytes, &s, qu8);
   if (rc) return rc;
   return scan_impl(s, c, image, rowinfo, img8, queries, nq, metric, k, mask, ws,
                    reinterpret_cast<hipStream_t>(stream));
@@ -515,9 +540,9 @@ static int reduce_impl(const SearchLayout& s, const fx_corpus& c, const float* q
 // equals the scan half's as long as no option changed in between
 static int reduce_call(const fx_corpus& c, bool img8, const float* queries, int64_t nq, int metric,
                        int64_t k, const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
-                       int64_t* out_row, void* stream) {
+                       int64_t* out_row, void* stream, bool qu8 = false) {
   SearchLayout s;
-  int rc = search_layout(c, nq, metric, k, img8, ws, ws_bytes, &s);
+  int rc = search_layout(c, nq, metric, k, img8, ws, ws_bytes, &s, qu8);
   if (rc) return rc;
   return reduce_impl(s, c, queries, nq, k, mask, ws, out_dist, out_row,
                      reinterpret_cast<hipStream_t>(stream));
@@ -527,13 +552,13 @@ static int reduce_call(const fx_corpus& c, bool img8, const float* queries, int6
 static int search_call(const fx_corpus& c, const void* image, const float* rowinfo, bool img8,
                        const float* queries, int64_t nq, int metric, int64_t k,
                        const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
-                       int64_t* out_row, void* stream) {
+                       int64_t* out_row, void* stream, bool qu8 = false) {
   if (!out_dist || !out_row) {
     set_error("null pointer argument");
     return FX_EINVAL;
   }
   SearchLayout s;
-  int rc = search_layout(c, nq, metric, k, img8 && image != nullptr, ws, ws_bytes, &s);
+  int rc = search_layout(c, nq, metric, k, img8 && image != nullptr, ws, ws_bytes, &s, qu8);
   if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   rc = scan_impl(s, c, image, rowinfo, img8, queries, nq, metric, k, mask, ws, st);
@@ -663,7 +688,7 @@ int fx_filter_image_used(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k,
     return FX_EINVAL;
   }
   *out = 0;
-  int rc = validate(n, d, dtype, nq, k, metric, false);
+  int rc = validate(n, d, dtype, nq, k, metric, true);
   if (rc) return rc;
   SearchLayout s;
   // (the int8 image, the host's default, also serves single queries over
@@ -681,7 +706,7 @@ int fx_knn_filter_state(const void* corpus, int dtype, int64_t n, int64_t d, int
                         void* stream) {
   SearchLayout s;
   int rc = search_layout(corpus_of(corpus, dtype, n, d, 0), nq, metric, k, img8 != 0, ws,
-                         ws_bytes, &s);
+                         ws_bytes, &s, true);
   if (rc) return rc;
   if (!s.batched || !s.batch.filter) {
     set_error("fx_knn_filter_state: the search did not run the filter");
@@ -709,7 +734,7 @@ int fx_knn_filter_counts(const void* corpus, int dtype, int64_t n, int64_t d, in
                          uint32_t* out_counts, int64_t* out_cap, void* stream) {
   SearchLayout s;
   int rc = search_layout(corpus_of(corpus, dtype, n, d, 0), nq, metric, k, img8 != 0, ws,
-                         ws_bytes, &s);
+                         ws_bytes, &s, true);
   if (rc) return rc;
   if (!out_counts || !out_cap) {
     set_error("null pointer argument");
@@ -768,6 +793,67 @@ int fx_knn_search_img8(const void* corpus, int dtype, int64_t n, int64_t d, int6
                        float* out_dist, int64_t* out_row, void* stream) {
   return search_call(corpus_of(corpus, dtype, n, d, row_base), image, rowinfo, true, queries, nq,
                      metric, k, mask, ws, ws_bytes, out_dist, out_row, stream);
+}
+
+// The descriptor forms of the int8-image entry points: any dtype, and the
+// only ones that take quint8 codes (their scale and zero point travel in the
+// fx_corpus).  Same plans and drivers as the plain-argument forms.
+static const fx_corpus* checked_corpus(const fx_corpus* c) {
+  if (c == nullptr || c->data == nullptr) {
+    set_error("null corpus");
+    return nullptr;
+  }
+  return c;
+}
+
+int fx_filter_image8_ex(const fx_corpus* c, void* image, float* rowinfo, void* stream) {
+  if (!checked_corpus(c)) return FX_EINVAL;
+  if (c->dtype != FX_DTYPE_QU8)
+    return fx_filter_image8_typed(c->data, c->dtype, c->n, c->d, image, rowinfo, stream);
+  size_t ib = 0, rb = 0;
+  int rc = fx_filter_image8_bytes(c->n, c->d, &ib, &rb);
+  if (rc) return rc;
+  if (c->d % 16 != 0 || c->d > 0x7fffffffll) {
+    set_error("filter image: quint8 rows need d %% 16 == 0, d=%lld", (long long)c->d);
+    return FX_EUNSUPPORTED;
+  }
+  rc = validate_quant(*c);
+  if (rc) return rc;
+  if (c->n > 0 && (!image || !rowinfo)) {
+    set_error("null pointer argument");
+    return FX_EINVAL;
+  }
+  if ((uintptr_t)c->data % 16 != 0 || (uintptr_t)image % 16 != 0 || (uintptr_t)rowinfo % 16 != 0) {
+    set_error("filter image: corpus, image and row info must be 16-byte aligned");
+    return FX_EINVAL;
+  }
+  return launch_image8(c->data, c->dtype, c->n, (int)c->d, image, rowinfo,
+                       reinterpret_cast<hipStream_t>(stream), Quant{c->scale, (float)c->zero_point});
+}
+
+int fx_knn_scan_img8_ex(const fx_corpus* c, const void* image, const float* rowinfo,
+                        const float* queries, int64_t nq, int metric, int64_t k,
+                        const uint32_t* mask, void* ws, size_t ws_bytes, void* stream) {
+  if (!checked_corpus(c)) return FX_EINVAL;
+  return scan_call(*c, image, rowinfo, true, queries, nq, metric, k, mask, ws, ws_bytes, stream,
+                   true);
+}
+
+int fx_knn_reduce_img8_ex(const fx_corpus* c, const void* image, const float* queries, int64_t nq,
+                          int metric, int64_t k, const uint32_t* mask, void* ws, size_t ws_bytes,
+                          float* out_dist, int64_t* out_row, void* stream) {
+  if (!checked_corpus(c)) return FX_EINVAL;
+  return reduce_call(*c, image != nullptr, queries, nq, metric, k, mask, ws, ws_bytes, out_dist,
+                     out_row, stream, true);
+}
+
+int fx_knn_search_img8_ex(const fx_corpus* c, const void* image, const float* rowinfo,
+                          const float* queries, int64_t nq, int metric, int64_t k,
+                          const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
+                          int64_t* out_row, void* stream) {
+  if (!checked_corpus(c)) return FX_EINVAL;
+  return search_call(*c, image, rowinfo, true, queries, nq, metric, k, mask, ws, ws_bytes,
+                     out_dist, out_row, stream, true);
 }
 
 // merges of lists longer than the fused path's k go through the radix sort

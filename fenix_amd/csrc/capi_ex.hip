@@ -3,7 +3,10 @@
 // the scan's registers, ex/arrow/quint8/quint8.py:81-84; optional row list
 // and mask), its plain-argument forms fx_knn_search_rows / fx_knn_distances,
 // and several shards under one merge.  Same plans and kernels as fx_knn_search
-// (knn_plan.hip plan_exact); no batched MFMA path here (it reads f32 rows).
+// (knn_plan.hip plan_exact).  Nothing here runs the batched filter: a batch
+// over quint8 codes takes it through the descriptor forms of the int8-image
+// entry points (capi.hip fx_knn_search_img8_ex), which fall back to these
+// plans when the gate says no.
 #include <vector>
 
 #include "fx_plan.h"
@@ -25,11 +28,8 @@ int check_corpus(const fx_corpus* c, int64_t nq, int64_t k, int metric) {
   }
   int rc = validate(c->n, c->d, c->dtype, nq, k, metric, true);
   if (rc) return rc;
-  if (c->dtype == FX_DTYPE_QU8 && (c->zero_point < 0 || c->zero_point > 255 ||
-                                   !(c->scale > 0.f) || c->scale == __builtin_inff())) {
-    set_error("quint8 zero_point %d / scale %g out of range", c->zero_point, (double)c->scale);
-    return FX_EINVAL;
-  }
+  rc = validate_quant(*c);
+  if (rc) return rc;
   return rows_fit(c->row_base, c->n) ? FX_OK : FX_EUNSUPPORTED;
 }
 

@@ -32,6 +32,8 @@ constexpr int kSelectMaxK = 2048;
 //   scan_stream          plain f32 / f16 scans: 1: streaming kernel, 0: register tiles, -1: by class
 //   filter_hold          1: the filter phases stop after their last filter pass, the bounds left
 //                        in the workspace for fx_knn_filter_state (test switch; no reduce follows)
+//   qu8_batch_min_work   quint8 batches go through an int8 image from nq * n * d code bytes on
+//                        (use_batched: below it a few exact scans beat the filter's fixed cost)
 #define FX_OPTIONS(FX_OPTION)                               \
   FX_OPTION(kOptBatched, "batched", 1)                      \
   FX_OPTION(kOptBatchMinQ, "batch_min_queries", 2)          \
@@ -50,7 +52,8 @@ constexpr int kSelectMaxK = 2048;
   FX_OPTION(kOptI8GrowRatio, "i8_grow_ratio", 16)           \
   FX_OPTION(kOptSelectPrune, "select_prune", 1)             \
   FX_OPTION(kOptScanStream, "scan_stream", -1)             \
-  FX_OPTION(kOptFilterHold, "filter_hold", 0)
+  FX_OPTION(kOptFilterHold, "filter_hold", 0)               \
+  FX_OPTION(kOptQu8BatchMinWork, "qu8_batch_min_work", 204800000)
 enum Option : int {
 #define FX_OPTION_ENUM(id, name, dflt) id,
   FX_OPTIONS(FX_OPTION_ENUM)
@@ -164,6 +167,13 @@ struct BatchArgs {
   float l2_eps;           // L2: relative error bound of |x|^2+|q|^2-2x.q in fp32
 };
 int launch_batch(const BatchArgs& a, int metric, hipStream_t stream);
+// FX_DTYPE_QU8 rows: value = scale * (code - shift), as ScanArgs::qscale / qshift
+// (f32 / f16 rows: unused)
+struct Quant {
+  float scale = 1.f, shift = 0.f;
+};
+// out [nq][d] = shift + q / scale: the quint8 L2 scan's query (scan_begin's expression)
+int launch_qu8_query(const float* Q, int64_t nq, int d, Quant z, float* out, hipStream_t stream);
 // mode 0: max(|q|, 1e-12) (cosine); mode 1: sum q^2 (L2 expansion)
 int launch_qnorm(const float* Q, int64_t nq, int d, float* out, hipStream_t stream,
                  int mode = 0);
@@ -171,15 +181,19 @@ int launch_qnorm(const float* Q, int64_t nq, int d, float* out, hipStream_t stre
 // summation order: bit-identical).  thr (optional): candidates whose key is
 // above the query's thr key are dropped (kEmpty) without being read.
 // qnorm: cosine only, max(|q|, 1e-12) as the scan computes it.
+// FX_DTYPE_QU8 (here and in the two launchers below; d % 16 == 0): z holds the
+// corpus's scale and zero point, and Q is what the quint8 scan keeps in LDS,
+// launch_qu8_query's q' for L2, the queries themselves otherwise.
 int launch_rescore(const void* X, int dtype, int64_t n, int d, int64_t row_base,
                    const float* Q, const float* qnorm, int64_t nq, const uint32_t* count,
-                   uint64_t* cand, int cap, int metric, const uint64_t* thr, hipStream_t stream);
+                   uint64_t* cand, int cap, int metric, const uint64_t* thr, hipStream_t stream,
+                   Quant z = Quant());
 // thr[q] = min(thr[q], the largest exact composite of the query's k rows
 // [nq][k] (global, -1 = missing: the query keeps its threshold)); scratch
 // [nq][2] uint64 zeroed before the first call (left zeroed by each call)
 int launch_exact_kth(const void* X, int dtype, int64_t n, int d, int64_t row_base,
                      const float* Q, const float* qnorm, int64_t nq, int k, int64_t* rows,
-                     int metric, uint64_t* thr, hipStream_t stream);
+                     int metric, uint64_t* thr, hipStream_t stream, Quant z = Quant());
 
 // run_merge (top-k by key of each query's first count[q] entries of keys
 // [nq][cap]) + launch_exact_kth in one launch, any cap (knn_batch.hip
@@ -197,7 +211,7 @@ int launch_exact_threshold(const void* X, int dtype, int64_t n, int d, int64_t r
                            int64_t cap, uint32_t* count, bool zero_count, int k, int metric,
                            uint64_t* thr, hipStream_t stream, uint64_t* prune, int prune_lists,
                            int64_t* topr, const uint64_t* gate_cand = nullptr,
-                           int64_t gate_num = 0, int64_t gate_den = 1);
+                           int64_t gate_num = 0, int64_t gate_den = 1, Quant z = Quant());
 // (gate_cand: launch_overflow_gate(gate_cand, count, thr, nq, cap, gate_num,
 // gate_den) follows on the new thresholds, fused into the select's workgroups
 // when the select computes them itself)
@@ -267,8 +281,10 @@ bool image_tiled();
 constexpr int kI8RowInfo = 4;
 constexpr int kI8QInfo = 4;
 constexpr float kI8Kappa = 128.f;
+// (FX_DTYPE_QU8: codes with z's scale and zero point, d % 16 == 0; same image
+// layout and row terms for the rows scale * (code - zero point))
 int launch_image8(const void* X, int dtype, int64_t n, int d, void* img, float* rowinfo,
-                  hipStream_t stream);
+                  hipStream_t stream, Quant z = Quant());
 // The int8 image stores its rows in the order of an affine permutation of the
 // corpus: image row i holds corpus row (a * i) % n, a ~ 0.618 n coprime with n
 // (a Weyl sequence).  The filter's nested samples take every r-th tile of the
@@ -289,9 +305,11 @@ int launch_overflow_gate(const uint64_t* cand, uint32_t* count, const uint64_t* 
                          int cap, int64_t num, int64_t den, hipStream_t stream);
 // (thr, count: when given, each query's threshold is set empty and its append
 // count zeroed in the same launch)
+// (qe, quint8 L2: Q holds launch_qu8_query's q', and the query the filter
+// bounds is the scan's effective one, qe->scale * (q' - qe->shift))
 int launch_qprep8(const float* Q, int64_t nq, int64_t nq_pad, int d, int dq, int metric,
                   int8_t* Qb, float* qinfo, hipStream_t stream, uint64_t* thr = nullptr,
-                  uint32_t* count = nullptr);
+                  uint32_t* count = nullptr, const Quant* qe = nullptr);
 int launch_qprep(const float* Q, int64_t nq, int64_t nq_pad, int d, int dq, int metric,
                  uint16_t* Qh, float* qinfo, hipStream_t stream);
 // rows per tile of every filter kernel (FilterArgs::tile_start ...)
@@ -311,6 +329,8 @@ int launch_fill(void* x, int dtype, int64_t n, int64_t d, uint64_t seed, int64_t
 void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 int check_launch(const char* what);
 int device_cus(int* out);
+// false on a host with no HIP device (plans are then answered for the target, plan_scan)
+bool device_present();
 int kernel_occupancy(const void* fn, int block, size_t smem, int* out);
 // raise the dynamic-LDS limit of fn to 160 KB on the current device (once per device)
 int allow_lds(const void* fn);

@@ -16,6 +16,9 @@ inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 // shape, dtype (qu8: FX_DTYPE_QU8 too), metric, then k in [1, kLargeMaxK];
 // an entry point without a k passes 1
 int validate(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, int metric, bool qu8);
+// a quint8 descriptor's zero point in [0, 255] and scale positive and finite
+// (other dtypes: nothing to check)
+int validate_quant(const fx_corpus& c);
 
 struct BatchLayout {
   int64_t cap = 0, tiles = 0, nq_pad = 0;
@@ -27,7 +30,7 @@ struct BatchLayout {
   int64_t start[16], stride[16], num[16];
   MergePlan merge;
   size_t off_qnorm, off_thr, off_count, off_cand, off_merge, off_cand_ub, off_qh, off_qinfo,
-      off_topr, off_prune, total;
+      off_topr, off_qt, off_prune, total;
 };
 
 struct SearchLayout {

@@ -95,6 +95,15 @@ static int current_device(int* dev) {
   return FX_OK;
 }
 
+bool device_present() {
+  static std::atomic<bool> seen{false};  // (a device does not go away; its absence is re-checked)
+  if (seen.load(std::memory_order_relaxed)) return true;
+  int count = 0;
+  const bool ok = hipGetDeviceCount(&count) == hipSuccess && count > 0;
+  if (ok) seen.store(true, std::memory_order_relaxed);
+  return ok;
+}
+
 int device_cus(int* out) {
   int dev = 0;
   if (int rc = current_device(&dev)) return rc;

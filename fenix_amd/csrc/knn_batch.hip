@@ -24,6 +24,8 @@
 // composite of ANY subset of rows upper-bounds the global k-th, so filtering
 // with it never drops a true top-k row (capi.hip: batched_phases).  The
 // buffers are then reduced by the ordinary merge kernels.
+#include <type_traits>
+
 #include "fx_internal.h"
 #include "fx_select.h"
 #include "fx_wave.h"
@@ -286,12 +288,85 @@ int launch_qnorm(const float* Q, int64_t nq, int d, float* out, hipStream_t stre
   return check_launch("qnorm_kernel");
 }
 
+// The quint8 L2 scan's query q' = shift + q / scale, element by element in
+// the f32 expression scan_begin (knn_scan.hip) evaluates on its way into LDS:
+// the rescoring reads it back instead of dividing per candidate, and
+// launch_qprep8 takes the filter's effective query from the same bits.
+__global__ void qu8_query_kernel(const float* __restrict__ Q, int64_t count, Quant z,
+                                 float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < count) out[i] = z.shift + Q[i] / z.scale;
+}
+
+int launch_qu8_query(const float* Q, int64_t nq, int d, Quant z, float* out, hipStream_t stream) {
+  const int64_t count = nq * d;
+  hipLaunchKernelGGL(qu8_query_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream,
+                     Q, count, z, out);
+  return check_launch("qu8_query_kernel");
+}
+
 // The single-query scan's f32 distance of one row, computed by a 16-lane
 // group (lane jl of the group): 16-B loads of the row and the query, the
 // scan's per-lane fmaf chain over slots jl, jl+16, ... (knn_scan.hip
 // tile_accumulate), its sum16 reduction and its distance formula
 // (tile_finish): bit for bit the scan's value.  Every lane of the wave must
 // call it (sum16 is a cross-lane reduction); live = false contributes zeros.
+//
+// quint8 codes (T = uint8_t, d % 16 == 0): the scan's code-unit arithmetic
+// instead, tile_accumulate's sizeof(T) == 1, W == 16 branch and tile_finish's
+// quint8 branch operation for operation.  Lane jl takes the 16-code slots
+// jl, jl + 16, ...; per slot the 8 packed pairs go through fma into a2 (b2:
+// the cosine's sum of squares), then acc += a2.x + a2.y.  qv is what the scan
+// keeps in LDS: q' = shift + q / scale for L2 (launch_qu8_query wrote it with
+// scan_begin's own f32 expression), q itself otherwise.  A slot past the row
+// (the scan pads with the zero-point code against q' = shift, or q = 0) adds
+// +0 to a sum that is never -0: skipped.
+template <int METRIC>
+__device__ __forceinline__ float exact_distance16_qu8(const uint8_t* __restrict__ xr,
+                                                      const float* __restrict__ qv, int d, int jl,
+                                                      bool live, float qnorm, Quant z) {
+  typedef uint8_t u8x16 __attribute__((ext_vector_type(16)));
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  typedef float f16v __attribute__((ext_vector_type(16)));
+  float acc = 0.f, acc2 = 0.f;
+  const f2 z2 = {z.shift, z.shift};
+  if (live) {
+    for (int k = jl * 16; k < d; k += 256) {
+      const f16v xf = __builtin_convertvector(*reinterpret_cast<const u8x16*>(xr + k), f16v);
+      f4 q4[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) q4[i] = *reinterpret_cast<const f4*>(qv + k + 4 * i);
+      f2 a2 = {0.f, 0.f}, b2 = {0.f, 0.f};
+#pragma unroll
+      for (int p = 0; p < 8; ++p) {
+        const f2 x2 = {xf[2 * p], xf[2 * p + 1]};
+        const f2 q2 = {q4[p >> 1][2 * (p & 1)], q4[p >> 1][2 * (p & 1) + 1]};
+        if constexpr (METRIC == 0) {
+          const f2 df = x2 - q2;
+          a2 = __builtin_elementwise_fma(df, df, a2);
+        } else {
+          const f2 df = x2 - z2;
+          a2 = __builtin_elementwise_fma(df, q2, a2);
+          if constexpr (METRIC == 2) b2 = __builtin_elementwise_fma(df, df, b2);
+        }
+      }
+      acc += a2.x + a2.y;
+      if constexpr (METRIC == 2) acc2 += b2.x + b2.y;
+    }
+  }
+  const float s1 = sum16(acc);
+  if constexpr (METRIC == 0) {
+    return z.scale * sqrtf(s1);
+  } else if constexpr (METRIC == 1) {
+    return -(z.scale * s1);
+  } else {
+    const float s2 = sum16(acc2);
+    const float nx = fmaxf(z.scale * sqrtf(s2), 1e-12f);
+    return 0.5f - 0.5f * ((z.scale * s1) / (nx * qnorm));
+  }
+}
+
 template <typename T, int METRIC>
 __device__ __forceinline__ float exact_distance16(const T* __restrict__ xr,
                                                   const float* __restrict__ qv, int d, int jl,
@@ -351,6 +426,19 @@ __device__ __forceinline__ float exact_distance16(const T* __restrict__ xr,
   }
 }
 
+// The row's scan distance by its type: exact_distance16 for f32 / f16 rows
+// (z unused), exact_distance16_qu8 for quint8 codes
+template <typename T, int METRIC>
+__device__ __forceinline__ float row_distance16(const T* __restrict__ xr,
+                                                const float* __restrict__ qv, int d, int jl,
+                                                bool live, float qnorm, Quant z) {
+  if constexpr (sizeof(T) == 1) {
+    return exact_distance16_qu8<METRIC>(xr, qv, d, jl, live, qnorm, z);
+  } else {
+    return exact_distance16<T, METRIC>(xr, qv, d, jl, live, qnorm);
+  }
+}
+
 // Exact distance of each appended candidate (exact_distance16); the key is
 // replaced in place (row unchanged).  With thr, a candidate whose
 // (lower-bound) key is above the query's threshold key is dropped (kEmpty)
@@ -370,7 +458,8 @@ __global__ void __launch_bounds__(256) rescore_dense_kernel(const T* __restrict_
                                                             const float* __restrict__ qnorm,
                                                             const uint32_t* __restrict__ count,
                                                             uint64_t* __restrict__ cand, int cap,
-                                                            const uint64_t* __restrict__ thr) {
+                                                            const uint64_t* __restrict__ thr,
+                                                            Quant z) {
   const int64_t q = blockIdx.y;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int grp = lane >> 4, jl = lane & 15;
@@ -387,7 +476,7 @@ __global__ void __launch_bounds__(256) rescore_dense_kernel(const T* __restrict_
     const int64_t row = (int64_t)(c & 0xffffffffull) - row_base;
     const bool keep = c != kEmpty && (uint32_t)(c >> 32) <= tkey && row >= 0 && row < n;
     const float dist =
-        exact_distance16<T, METRIC>(X + (keep ? row : 0) * (int64_t)d, qv, d, jl, keep, qn);
+        row_distance16<T, METRIC>(X + (keep ? row : 0) * (int64_t)d, qv, d, jl, keep, qn, z);
     if (jl == 0 && c != kEmpty)
       cl[i] = keep ? make_comp(dist, (uint32_t)(c & 0xffffffffull)) : kEmpty;
   }
@@ -400,7 +489,7 @@ __global__ void __launch_bounds__(256) rescore_kernel(const T* __restrict__ X, i
                                                       const float* __restrict__ qnorm,
                                                       const uint32_t* __restrict__ count,
                                                       uint64_t* __restrict__ cand, int cap,
-                                                      const uint64_t* __restrict__ thr) {
+                                                      const uint64_t* __restrict__ thr, Quant z) {
   const int64_t q = blockIdx.y;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int grp = lane >> 4, jl = lane & 15;
@@ -432,7 +521,7 @@ __global__ void __launch_bounds__(256) rescore_kernel(const T* __restrict__ X, i
       const int64_t rs = (int64_t)lo - row_base;
       const bool live = src >= 0;
       const float dist =
-          exact_distance16<T, METRIC>(X + (live ? rs : 0) * (int64_t)d, qv, d, jl, live, qn);
+          row_distance16<T, METRIC>(X + (live ? rs : 0) * (int64_t)d, qv, d, jl, live, qn, z);
       if (jl == 0 && live) cl[base + src] = make_comp(dist, (uint32_t)(cs & 0xffffffffull));
     }
   }
@@ -454,7 +543,7 @@ __global__ void __launch_bounds__(256) exact_kth_kernel(const T* __restrict__ X,
                                                         int64_t row_base,
                                                         const float* __restrict__ Q,
                                                         const float* __restrict__ qnorm, int k,
-                                                        int64_t* __restrict__ rows) {
+                                                        int64_t* __restrict__ rows, Quant z) {
   const int64_t q = blockIdx.y;
   const int grp = threadIdx.x >> 4, jl = threadIdx.x & 15;
   const int j = blockIdx.x * 16 + grp;
@@ -462,8 +551,8 @@ __global__ void __launch_bounds__(256) exact_kth_kernel(const T* __restrict__ X,
   const int64_t row = grow - row_base;
   const bool live = j < k && grow >= 0 && row >= 0 && row < n;
   const float qn = METRIC == 2 ? qnorm[q] : 0.f;
-  const float dist = exact_distance16<T, METRIC>(X + (live ? row : 0) * (int64_t)d,
-                                                 Q + q * (int64_t)d, d, jl, live, qn);
+  const float dist = row_distance16<T, METRIC>(X + (live ? row : 0) * (int64_t)d,
+                                               Q + q * (int64_t)d, d, jl, live, qn, z);
   if (jl == 0 && j < k)
     rows[q * (int64_t)k + j] = live ? (int64_t)make_comp(dist, (uint32_t)grow) : (int64_t)kEmpty;
 }
@@ -486,7 +575,8 @@ __global__ void __launch_bounds__(256) kth_max_kernel(const uint64_t* __restrict
 template <typename T>
 static void launch_rescore_t(const T* X, int64_t n, int d, int64_t row_base, const float* Q,
                              const float* qnm, const uint32_t* count, uint64_t* cand, int cap,
-                             int metric, const uint64_t* t, dim3 grid, hipStream_t stream) {
+                             int metric, const uint64_t* t, dim3 grid, hipStream_t stream,
+                             Quant z) {
   if (grid.y <= kRescoreDenseMaxQ) {
     // (one slot per 16-lane group: 16 K slots per grid step, fewer blocks
     // when the buffer is smaller)
@@ -495,30 +585,30 @@ static void launch_rescore_t(const T* X, int64_t n, int d, int64_t row_base, con
     g2.x = (unsigned)(need < 1024 ? need : 1024);
     if (metric == FX_METRIC_COS)
       hipLaunchKernelGGL((rescore_dense_kernel<T, 2>), g2, dim3(256), 0, stream, X, n, d,
-                         row_base, Q, qnm, count, cand, cap, t);
+                         row_base, Q, qnm, count, cand, cap, t, z);
     else if (metric == FX_METRIC_IP)
       hipLaunchKernelGGL((rescore_dense_kernel<T, 1>), g2, dim3(256), 0, stream, X, n, d,
-                         row_base, Q, qnm, count, cand, cap, t);
+                         row_base, Q, qnm, count, cand, cap, t, z);
     else
       hipLaunchKernelGGL((rescore_dense_kernel<T, 0>), g2, dim3(256), 0, stream, X, n, d,
-                         row_base, Q, qnm, count, cand, cap, t);
+                         row_base, Q, qnm, count, cand, cap, t, z);
     return;
   }
   if (metric == FX_METRIC_COS) {
     hipLaunchKernelGGL((rescore_kernel<T, 2>), grid, dim3(256), 0, stream, X, n, d, row_base, Q,
-                       qnm, count, cand, cap, t);
+                       qnm, count, cand, cap, t, z);
   } else if (metric == FX_METRIC_IP) {
     hipLaunchKernelGGL((rescore_kernel<T, 1>), grid, dim3(256), 0, stream, X, n, d, row_base, Q,
-                       qnm, count, cand, cap, t);
+                       qnm, count, cand, cap, t, z);
   } else {
     hipLaunchKernelGGL((rescore_kernel<T, 0>), grid, dim3(256), 0, stream, X, n, d, row_base, Q,
-                       qnm, count, cand, cap, t);
+                       qnm, count, cand, cap, t, z);
   }
 }
 
 int launch_rescore(const void* X, int dtype, int64_t n, int d, int64_t row_base, const float* Q,
                    const float* qnorm, int64_t nq, const uint32_t* count, uint64_t* cand,
-                   int cap, int metric, const uint64_t* thr, hipStream_t stream) {
+                   int cap, int metric, const uint64_t* thr, hipStream_t stream, Quant z) {
   int cus = 0;
   int rc = device_cus(&cus);
   if (rc) return rc;
@@ -533,12 +623,15 @@ int launch_rescore(const void* X, int dtype, int64_t n, int d, int64_t row_base,
     const float* qnm = qnorm != nullptr ? qnorm + q0 : nullptr;
     const uint32_t* cn = count + q0 * kCountStride;
     uint64_t* cd = cand + q0 * (int64_t)cap;
-    if (dtype == FX_DTYPE_F16) {
+    if (dtype == FX_DTYPE_QU8) {
+      launch_rescore_t(reinterpret_cast<const uint8_t*>(X), n, d, row_base, Q + q0 * d, qnm, cn,
+                       cd, cap, metric, t, grid, stream, z);
+    } else if (dtype == FX_DTYPE_F16) {
       launch_rescore_t(reinterpret_cast<const _Float16*>(X), n, d, row_base, Q + q0 * d, qnm, cn,
-                       cd, cap, metric, t, grid, stream);
+                       cd, cap, metric, t, grid, stream, z);
     } else {
       launch_rescore_t(reinterpret_cast<const float*>(X), n, d, row_base, Q + q0 * d, qnm, cn, cd,
-                       cap, metric, t, grid, stream);
+                       cap, metric, t, grid, stream, z);
     }
     rc = check_launch("rescore_kernel");
     if (rc) return rc;
@@ -549,32 +642,35 @@ int launch_rescore(const void* X, int dtype, int64_t n, int d, int64_t row_base,
 template <typename T>
 static void launch_exact_kth_t(const T* X, int64_t n, int d, int64_t row_base, const float* Q,
                                const float* qnm, int k, int64_t* rows, int metric, dim3 grid,
-                               hipStream_t stream) {
+                               hipStream_t stream, Quant z) {
   if (metric == FX_METRIC_COS) {
     hipLaunchKernelGGL((exact_kth_kernel<T, 2>), grid, dim3(256), 0, stream, X, n, d, row_base,
-                       Q, qnm, k, rows);
+                       Q, qnm, k, rows, z);
   } else if (metric == FX_METRIC_IP) {
     hipLaunchKernelGGL((exact_kth_kernel<T, 1>), grid, dim3(256), 0, stream, X, n, d, row_base,
-                       Q, qnm, k, rows);
+                       Q, qnm, k, rows, z);
   } else {
     hipLaunchKernelGGL((exact_kth_kernel<T, 0>), grid, dim3(256), 0, stream, X, n, d, row_base,
-                       Q, qnm, k, rows);
+                       Q, qnm, k, rows, z);
   }
 }
 
 int launch_exact_kth(const void* X, int dtype, int64_t n, int d, int64_t row_base,
                      const float* Q, const float* qnorm, int64_t nq, int k, int64_t* rows,
-                     int metric, uint64_t* thr, hipStream_t stream) {
+                     int metric, uint64_t* thr, hipStream_t stream, Quant z) {
   for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
     const int64_t qn = (nq - q0) < 65535 ? (nq - q0) : 65535;
     const dim3 grid((unsigned)((k + 15) / 16), (unsigned)qn);
     const float* qnm = qnorm != nullptr ? qnorm + q0 : nullptr;
-    if (dtype == FX_DTYPE_F16) {
+    if (dtype == FX_DTYPE_QU8) {
+      launch_exact_kth_t(reinterpret_cast<const uint8_t*>(X), n, d, row_base, Q + q0 * d, qnm, k,
+                         rows + q0 * k, metric, grid, stream, z);
+    } else if (dtype == FX_DTYPE_F16) {
       launch_exact_kth_t(reinterpret_cast<const _Float16*>(X), n, d, row_base, Q + q0 * d, qnm, k,
-                         rows + q0 * k, metric, grid, stream);
+                         rows + q0 * k, metric, grid, stream, z);
     } else {
       launch_exact_kth_t(reinterpret_cast<const float*>(X), n, d, row_base, Q + q0 * d, qnm, k,
-                         rows + q0 * k, metric, grid, stream);
+                         rows + q0 * k, metric, grid, stream, z);
     }
     int rc = check_launch("exact_kth_kernel");
     if (rc) return rc;
@@ -659,7 +755,8 @@ __global__ void __launch_bounds__(kSelectThreads)
                   float* __restrict__ out_dist, int64_t* __restrict__ out_row,
                   const uint64_t* __restrict__ alt, int64_t alt_m, int64_t alt_gate,
                   uint64_t* __restrict__ pre, int pre_p, int64_t pre_s,
-                  const uint64_t* __restrict__ gate_cand, int64_t gate_num, int64_t gate_den) {
+                  const uint64_t* __restrict__ gate_cand, int64_t gate_num, int64_t gate_den,
+                  Quant z) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   MergeShared* ms = reinterpret_cast<MergeShared*>(smem);
   uint64_t* res = reinterpret_cast<uint64_t*>(smem + sizeof(MergeShared));
@@ -794,8 +891,8 @@ __global__ void __launch_bounds__(kSelectThreads)
       const int64_t grow = (int64_t)(e & 0xffffffffull);
       const int64_t row = grow - row_base;
       const bool live = j < nres && e != kEmpty && row >= 0 && row < n;
-      const float dist = exact_distance16<T, METRIC>(X + (live ? row : 0) * (int64_t)d, qv, d,
-                                                     jl, live, qn);
+      const float dist = row_distance16<T, METRIC>(X + (live ? row : 0) * (int64_t)d, qv, d, jl,
+                                                   live, qn, z);
       // a missing or out-of-shard row: the largest composite (no threshold)
       const uint64_t comp = live ? make_comp(dist, (uint32_t)grow) : kEmpty;
       if (j < k) mx = comp > mx ? comp : mx;
@@ -895,7 +992,7 @@ static int launch_select_one(const T* X, int64_t n, int d, int64_t row_base, con
                              float* out_dist, int64_t* out_row, const uint64_t* alt,
                              int64_t alt_m, int64_t alt_gate, uint64_t* pre, int pre_p,
                              hipStream_t stream, const uint64_t* gate_cand = nullptr,
-                             int64_t gate_num = 0, int64_t gate_den = 1) {
+                             int64_t gate_num = 0, int64_t gate_den = 1, Quant z = Quant()) {
   const void* fn = metric == FX_METRIC_COS  ? (const void*)select_kernel<T, 2, MODE>
                    : metric == FX_METRIC_IP ? (const void*)select_kernel<T, 1, MODE>
                                             : (const void*)select_kernel<T, 0, MODE>;
@@ -922,7 +1019,7 @@ static int launch_select_one(const T* X, int64_t n, int d, int64_t row_base, con
                     (void*)&qnm, (void*)&kq,    (void*)&cap,   (void*)&cq,       (void*)&zero,
                     (void*)&k,   (void*)&P2,    (void*)&tq,    (void*)&od,       (void*)&orow,
                     (void*)&aq,  (void*)&alt_m, (void*)&alt_gate, (void*)&pq,    (void*)&pre_p,
-                    (void*)&pre_s, (void*)&gq, (void*)&gate_num, (void*)&gate_den};
+                    (void*)&pre_s, (void*)&gq, (void*)&gate_num, (void*)&gate_den, (void*)&z};
     hipError_t e = hipLaunchKernel(fn, dim3(gx, (unsigned)qn), dim3(kSelectThreads), args, smem,
                                    stream);
     if (e != hipSuccess) {
@@ -943,7 +1040,7 @@ static int launch_select_t(const T* X, int64_t n, int d, int64_t row_base, const
                            float* out_dist, int64_t* out_row, const uint64_t* alt,
                            int64_t alt_m, int64_t alt_gate, hipStream_t stream, uint64_t* pre,
                            int pre_p, const uint64_t* gate_cand = nullptr,
-                           int64_t gate_num = 0, int64_t gate_den = 1) {
+                           int64_t gate_num = 0, int64_t gate_den = 1, Quant z = Quant()) {
   if (pre == nullptr) pre_p = 0;
   if (pre_p <= 0) pre = nullptr;
   if (pre != nullptr) {
@@ -954,7 +1051,7 @@ static int launch_select_t(const T* X, int64_t n, int d, int64_t row_base, const
   }
   return launch_select_one<T, MODE>(X, n, d, row_base, Q, qnorm, nq, keys, cap, count, zero, k,
                                     metric, thr, out_dist, out_row, alt, alt_m, alt_gate, pre,
-                                    pre_p, stream, gate_cand, gate_num, gate_den);
+                                    pre_p, stream, gate_cand, gate_num, gate_den, z);
 }
 
 int launch_exact_threshold(const void* X, int dtype, int64_t n, int d, int64_t row_base,
@@ -962,7 +1059,7 @@ int launch_exact_threshold(const void* X, int dtype, int64_t n, int d, int64_t r
                            int64_t cap, uint32_t* count, bool zero_count, int k, int metric,
                            uint64_t* thr, hipStream_t stream, uint64_t* prune, int prune_lists,
                            int64_t* topr, const uint64_t* gate_cand, int64_t gate_num,
-                           int64_t gate_den) {
+                           int64_t gate_den, Quant z) {
   if (k > kSelectMaxK || k > cap) {
     set_error("exact threshold: k %d beyond cap %lld", k, (long long)cap);
     return FX_EUNSUPPORTED;
@@ -972,32 +1069,24 @@ int launch_exact_threshold(const void* X, int dtype, int64_t n, int d, int64_t r
               (long long)gate_den, (int)zero_count);
     return FX_EINVAL;
   }
-  if (prune != nullptr && topr != nullptr && prune_lists > 0) {
-    // large k: the pruned select writes the k rows, the chip rescores them
-    // (one workgroup rescoring 1 000 rows of 3 KB took ~40 us of its time)
-    int rc = dtype == FX_DTYPE_F16
-                 ? launch_select_t<_Float16, 0>(reinterpret_cast<const _Float16*>(X), n, d,
-                                                row_base, Q, qnorm, nq, keys, cap, count,
-                                                zero_count ? 1 : 0, k, metric, thr, nullptr, topr,
-                                                nullptr, 0, 0, stream, prune, prune_lists)
-                 : launch_select_t<float, 0>(reinterpret_cast<const float*>(X), n, d, row_base, Q,
-                                             qnorm, nq, keys, cap, count, zero_count ? 1 : 0, k,
-                                             metric, thr, nullptr, topr, nullptr, 0, 0, stream,
-                                             prune, prune_lists);
-    if (rc) return rc;
-    rc = launch_exact_kth(X, dtype, n, d, row_base, Q, qnorm, nq, k, topr, metric, thr, stream);
-    if (rc || gate_cand == nullptr) return rc;
-    return launch_overflow_gate(gate_cand, count, thr, nq, (int)cap, gate_num, gate_den, stream);
-  }
-  if (dtype == FX_DTYPE_F16)
-    return launch_select_t<_Float16, 0>(reinterpret_cast<const _Float16*>(X), n, d, row_base, Q,
-                                        qnorm, nq, keys, cap, count, zero_count ? 1 : 0, k, metric,
-                                        thr, nullptr, nullptr, nullptr, 0, 0, stream, prune,
-                                        prune_lists, gate_cand, gate_num, gate_den);
-  return launch_select_t<float, 0>(reinterpret_cast<const float*>(X), n, d, row_base, Q, qnorm, nq,
-                                   keys, cap, count, zero_count ? 1 : 0, k, metric, thr, nullptr,
-                                   nullptr, nullptr, 0, 0, stream, prune, prune_lists, gate_cand,
-                                   gate_num, gate_den);
+  // large k: the pruned select writes the k rows, the chip rescores them
+  // (one workgroup rescoring 1 000 rows of 3 KB took ~40 us of its time)
+  const bool rows_out = prune != nullptr && topr != nullptr && prune_lists > 0;
+  auto select = [&](auto* x) {
+    using T = std::remove_cv_t<std::remove_pointer_t<decltype(x)>>;
+    return launch_select_t<T, 0>(x, n, d, row_base, Q, qnorm, nq, keys, cap, count,
+                                 zero_count ? 1 : 0, k, metric, thr, nullptr,
+                                 rows_out ? topr : nullptr, nullptr, 0, 0, stream, prune,
+                                 prune_lists, rows_out ? nullptr : gate_cand,
+                                 rows_out ? 0 : gate_num, rows_out ? 1 : gate_den, z);
+  };
+  int rc = dtype == FX_DTYPE_QU8   ? select(reinterpret_cast<const uint8_t*>(X))
+           : dtype == FX_DTYPE_F16 ? select(reinterpret_cast<const _Float16*>(X))
+                                   : select(reinterpret_cast<const float*>(X));
+  if (rc || !rows_out) return rc;
+  rc = launch_exact_kth(X, dtype, n, d, row_base, Q, qnorm, nq, k, topr, metric, thr, stream, z);
+  if (rc || gate_cand == nullptr) return rc;
+  return launch_overflow_gate(gate_cand, count, thr, nq, (int)cap, gate_num, gate_den, stream);
 }
 
 int launch_sample_threshold(const uint64_t* keys, int64_t nq, int64_t cap, uint32_t* count,

@@ -431,6 +431,141 @@ __global__ void __launch_bounds__(256) image8_kernel(const T* __restrict__ X, in
   }
 }
 
+// The same image and row terms for quint8 codes (FX_DTYPE_QU8): the rows are
+// x = sigma y with y = code - zero point, integers in [-255, 255], and the
+// quint8 scan (knn_scan.hip tile_accumulate's sizeof(T) == 1 branch,
+// tile_finish) never forms x: it sums in code units and multiplies by sigma
+// at the end.  Everything below is derived from the integers.
+//
+// Row terms.  Y2 = sum y^2 is an exact integer.  The row is quantised in code
+// units, t = max(max|y| / 127, sqrt(Y2) / i8_norm_cap(d)), x~ = rint(y / t)
+// clamped to [-127, 127] (however t and x~ came out, the terms describe the x~
+// that was written), so its scale is s = sigma t and
+//   x - s x~ = sigma (y - t x~).
+// t x~ has at most 31 significant bits and y - t x~ is exact in double for
+// t >= 2^-22 (t >= 1/127 for a non-zero row), so e_c = |y - t x~| comes from
+// a double sum of exact squares (relative error d 2^-53, covered by 1e-12),
+// and w^2 = sum x~^2 is an exact integer.  sigma cancels in v = e / s = e_c / t:
+//   omega = w + kappa e_c / t         (double, rounded up to f32)
+//   1/s   = 1 / (sigma t),   N/s = sqrt(Y2) / t,   n^2/s = sigma Y2 / t
+// each the f32 nearest to its double value (N = max(sigma sqrt(Y2), 1e-12)):
+// one rounding u per term, where the f32 builder above carries the f32 sums'
+// g in n^2 and N; the kernels' constants (filter/tiled.inc) allow g + 16 u.
+// A zero row takes s = 1 like the f32 builder's.  Forced (omega = NaN): a row
+// whose integer image exceeds norm 2048, or one of whose terms leaves the f32
+// range (sigma below ~1e-30 or above ~1e30); no quint8 row is non-finite.
+//
+// What the bounds are held against (filter/tiled.inc, "int8 filter image";
+// u = 2^-24, g = (d + 2) u 1.01; d % 16 == 0, so d >= 16).  Every term of the
+// scan's sums passes 8 fmas of its pair chain, the a2.x + a2.y add, at most
+// ceil(d / 256) adds into acc and the 4 of sum16: r = 13 + ceil(d / 256)
+// roundings, and r + 3 <= d + 2 for every d >= 16.
+//   IP   s1 = sum y q (1 + th_i), |th_i| <= r u (y = code - zp is exact), and
+//        the distance is -fl(sigma s1): within (r + 1) u (1 + u) |x||q| <= g |x||q|
+//        of -x.q, the budget launch_qprep8 puts into P and R.  q is the query.
+//   cos  the same s1, s2 = sum y^2 within r u, then sigma s1, sigma sqrt(s2),
+//        the product of the norms, the division and 0.5 - 0.5 r: under
+//        2 r u + 8 u, plus the g / 2 of the scan's f32 |q| as for f32 rows,
+//        on 0.5 - 0.5 cos against the constant c = 3 g + 16 u.
+//        The cosine of sigma y is the cosine of y.  q is the query.
+//   L2   the scan compares codes with q' = fl(zp + fl(q / sigma)), so what it
+//        measures is the distance to the EFFECTIVE query qe = sigma (q' - zp):
+//        sigma^2 sum (code - q')^2 = |x - qe|^2 exactly.  Against the raw q
+//        the two differ by u (sigma zp sqrt(d) + |q|), absolute, which no
+//        relative slack covers when zp is far from the codes or q is almost a
+//        row.  launch_qprep8 is therefore given qe, evaluated in double from
+//        the scan's own q' bits (launch_qu8_query; the product rounds to
+//        2^-53, below R' >= P / kappa by 2^-46).  What is left is relative:
+//        fl(code - q') twice per square (2 u), the sums (r u), the square root
+//        and the final sigma multiply (4 u on the square): (r + 6) u < g2 =
+//        2 g + 8 u on |x - qe|^2.  n_q^2 and |q| of the record are qe's.
+// So the quint8 image needs no wider omega or query record than the f32 one:
+// the constants of filter/tiled.inc are untouched.
+__global__ void __launch_bounds__(256) image8_qu8_kernel(const uint8_t* __restrict__ X, int64_t n,
+                                                        int d, int8_t* __restrict__ img,
+                                                        float* __restrict__ rowinfo, uint64_t pa,
+                                                        Quant z) {
+  typedef uint8_t u8x16 __attribute__((ext_vector_type(16)));
+  const int lane = threadIdx.x & 63, h = lane >> 5;
+  const int64_t nt = (n + 31) / 32;
+  const int ksteps = (d + 31) / 32;
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  const int zp = (int)z.shift;
+  for (int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); t < nt; t += nw) {
+    const int64_t r = t * 32 + (lane & 31);
+    const bool live = r < n;
+    const uint8_t* xr = X + (live ? (int64_t)perm_row(pa, n, r) : 0) * (int64_t)d;
+    // y of components 32 ks + 16 h .. + 15 (zeros past d and in padding rows)
+    auto load = [&](int ks, int (&y)[16]) {
+      const int k0 = 32 * ks + 16 * h;
+      const bool ok = live && k0 < d;
+      const u8x16 c = *reinterpret_cast<const u8x16*>(xr + (ok ? k0 : 0));
+#pragma unroll
+      for (int e = 0; e < 16; ++e) y[e] = ok ? (int)c[e] - zp : 0;
+    };
+    int my = 0;
+    unsigned long long y2 = 0ull;
+    for (int ks = 0; ks < ksteps; ++ks) {
+      int y[16];
+      load(ks, y);
+      unsigned part = 0u;  // (16 squares of at most 255^2)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        part += (unsigned)(y[e] * y[e]);
+        my = max(my, abs(y[e]));
+      }
+      y2 += part;
+    }
+    y2 += __shfl_xor(y2, 32);
+    my = max(my, __shfl_xor(my, 32));
+    const double ny = sqrt((double)y2);
+    float tc = fmaxf((float)my * (1.f / 127.f), (float)(ny / (double)i8_norm_cap(d)) * (1.f + 1e-6f));
+    if (my == 0) tc = 1.f;  // zero row: x~ = 0 under any scale
+    const float it = 1.f / tc;
+    int w2 = 0;
+    double e2 = 0.0;
+    int8_t* out = img + (t * ksteps) * 1024 + lane * 16;
+    for (int ks = 0; ks < ksteps; ++ks) {
+      int y[16];
+      load(ks, y);
+      int32_t packed[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        uint32_t word = 0u;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const int yi = y[4 * j + b];
+          const float qf = fminf(fmaxf(rintf((float)yi * it), -127.f), 127.f);
+          const int qi = (int)qf;
+          w2 += qi * qi;
+          const double res = (double)yi - (double)tc * (double)qi;  // exact
+          e2 = fma(res, res, e2);
+          word |= ((uint32_t)qi & 0xffu) << (8 * b);
+        }
+        packed[j] = (int32_t)word;
+      }
+      *reinterpret_cast<int4*>(out + ks * 1024) = make_int4(packed[0], packed[1], packed[2], packed[3]);
+    }
+    w2 += __shfl_xor(w2, 32);
+    e2 += __shfl_xor(e2, 32);
+    if (h == 0 && live) {
+      const double w = sqrt((double)w2);
+      const double ec = sqrt(e2) * (1.0 + 1e-12);
+      const double om = (w + (double)kI8Kappa * (ec / (double)tc)) * (1.0 + 1e-12);
+      const double s = my == 0 ? 1.0 : (double)z.scale * (double)tc;
+      const double nn = fmax((double)z.scale * ny, 1e-12);
+      const float is = (float)(1.0 / s), y1n = (float)(nn / s);
+      const float y1l = (float)((double)z.scale * (double)z.scale * (double)y2 / s);
+      float omf = __double2float_ru(om);
+      if (w > 2048.0 || !(s > 1e-30) || !(is <= 3.4e38f) || !(y1n <= 3.4e38f) ||
+          !(y1l <= 3.4e38f) || !(omf <= 3.4e38f))
+        omf = __builtin_nanf("");
+      const img_f32x4 info = {omf, is, y1n, y1l};
+      *reinterpret_cast<img_f32x4*>(rowinfo + r * kI8RowInfo) = info;
+    }
+  }
+}
+
 static uint64_t gcd64(uint64_t a, uint64_t b) {
   while (b != 0) {
     const uint64_t t = a % b;
@@ -495,7 +630,7 @@ int launch_overflow_gate(const uint64_t* cand, uint32_t* count, const uint64_t* 
 }
 
 int launch_image8(const void* X, int dtype, int64_t n, int d, void* img, float* rowinfo,
-                  hipStream_t stream) {
+                  hipStream_t stream, Quant z) {
   if (n <= 0) return FX_OK;
   int cus = 0;
   int rc = device_cus(&cus);
@@ -503,7 +638,11 @@ int launch_image8(const void* X, int dtype, int64_t n, int d, void* img, float* 
   int64_t blocks = ((n + 31) / 32 + 3) / 4;
   if (blocks > (int64_t)cus * 8) blocks = (int64_t)cus * 8;
   const uint64_t pa = image8_perm(n);
-  if (dtype == FX_DTYPE_F16)
+  if (dtype == FX_DTYPE_QU8)
+    hipLaunchKernelGGL(image8_qu8_kernel, dim3((unsigned)blocks), dim3(256), 0, stream,
+                       reinterpret_cast<const uint8_t*>(X), n, d, reinterpret_cast<int8_t*>(img),
+                       rowinfo, pa, z);
+  else if (dtype == FX_DTYPE_F16)
     hipLaunchKernelGGL(image8_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, stream,
                        reinterpret_cast<const _Float16*>(X), n, d, reinterpret_cast<int8_t*>(img),
                        rowinfo, pa);
@@ -520,10 +659,15 @@ int launch_image8(const void* X, int dtype, int64_t n, int d, void* img, float* 
 // R' = max(R, P / kappa) (see "int8 filter image"); sums in double (products
 // of f32 and of f32 x int8 are exact there).  A non-finite query, or one whose
 // integer image exceeds norm 2048: R' = +inf (forced).
+// QE (quint8 L2, see image8_qu8_kernel): Q holds the scan's q', and the
+// query is qe = ze.scale * (q' - ze.shift) in double (q' - shift is exact,
+// the product rounds to 2^-53: with the residual's subtraction below, far
+// inside R' >= P / kappa and its 1e-6).
+template <bool QE>
 __global__ void qprep8_kernel(const float* __restrict__ Q, int64_t nq, int64_t nq_pad, int d,
                               int dq, int metric, int8_t* __restrict__ Qb,
                               float* __restrict__ qinfo, uint64_t* __restrict__ thr,
-                              uint32_t* __restrict__ count) {
+                              uint32_t* __restrict__ count, Quant ze) {
   const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (q >= nq_pad) return;
@@ -539,11 +683,15 @@ __global__ void qprep8_kernel(const float* __restrict__ Q, int64_t nq, int64_t n
     return;
   }
   const float* qv = Q + q * (int64_t)d;
+  auto val = [&](int i) -> double {
+    if constexpr (QE) return (double)ze.scale * ((double)qv[i] - (double)ze.shift);
+    return (double)qv[i];
+  };
   double s2 = 0.0;
   float m = 0.f;
   for (int i = lane; i < d; i += 64) {
-    s2 = fma((double)qv[i], (double)qv[i], s2);
-    m = fmaxf(m, fabsf(qv[i]));
+    s2 = fma(val(i), val(i), s2);
+    m = fmaxf(m, QE ? __double2float_ru(fabs(val(i))) : fabsf(qv[i]));
   }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) {
@@ -561,10 +709,10 @@ __global__ void qprep8_kernel(const float* __restrict__ Q, int64_t nq, int64_t n
   for (int i = lane; i < dq; i += 64) {
     int qi = 0;
     if (i < d && finite) {
-      float qf = rintf(qv[i] * is);
+      float qf = rintf((QE ? (float)val(i) : qv[i]) * is);
       qf = fminf(fmaxf(qf, -127.f), 127.f);
       qi = (int)qf;
-      const double r = (double)qv[i] - (double)sc * (double)qi;  // exact
+      const double r = val(i) - (double)sc * (double)qi;  // exact (QE: to 2^-53)
       e2 = fma(r, r, e2);
     }
     w2 += qi * qi;
@@ -596,9 +744,15 @@ __global__ void qprep8_kernel(const float* __restrict__ Q, int64_t nq, int64_t n
 }
 
 int launch_qprep8(const float* Q, int64_t nq, int64_t nq_pad, int d, int dq, int metric,
-                  int8_t* Qb, float* qinfo, hipStream_t stream, uint64_t* thr, uint32_t* count) {
-  hipLaunchKernelGGL(qprep8_kernel, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0, stream, Q,
-                     nq, nq_pad, d, dq, metric, Qb, qinfo, thr, count);
+                  int8_t* Qb, float* qinfo, hipStream_t stream, uint64_t* thr, uint32_t* count,
+                  const Quant* qe) {
+  const dim3 grid((unsigned)((nq_pad + 3) / 4));
+  if (qe != nullptr)
+    hipLaunchKernelGGL(qprep8_kernel<true>, grid, dim3(256), 0, stream, Q, nq, nq_pad, d, dq,
+                       metric, Qb, qinfo, thr, count, *qe);
+  else
+    hipLaunchKernelGGL(qprep8_kernel<false>, grid, dim3(256), 0, stream, Q, nq, nq_pad, d, dq,
+                       metric, Qb, qinfo, thr, count, Quant());
   return check_launch("qprep8_kernel");
 }
 

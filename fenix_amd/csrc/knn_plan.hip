@@ -28,6 +28,15 @@ int validate(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, int metric,
   return FX_OK;
 }
 
+int validate_quant(const fx_corpus& c) {
+  if (c.dtype == FX_DTYPE_QU8 && (c.zero_point < 0 || c.zero_point > 255 || !(c.scale > 0.f) ||
+                                  c.scale == __builtin_inff())) {
+    set_error("quint8 zero_point %d / scale %g out of range", c.zero_point, (double)c.scale);
+    return FX_EINVAL;
+  }
+  return FX_OK;
+}
+
 // ---------------------------------------------------------------- batched --
 //
 // Batched queries (nq >= kBatchMinQ, f32) run the MFMA kernel of knn_batch.hip
@@ -62,9 +71,30 @@ static constexpr int64_t kSingleImageMinBytes = (int64_t)4 << 30;
 // faster too (profiles/r06_kbatch_i8_max_k.jsonl).
 static int64_t i8_max_k() { return option(kOptI8MaxK); }
 
+// quint8 codes have no filter kernel of their own: a batch of them runs the
+// int8-MFMA filter over an int8 image of the dequantised rows
+// (image8_qu8_kernel) and is rescored from the codes in the quint8 scan's
+// arithmetic (exact_distance16_qu8, whole 16-code slots: d % 16 == 0).  A
+// single query stays on the scan (784 image bytes per 768 code bytes: nothing
+// to gain), and so does a batch of less than option "qu8_batch_min_work"
+// code bytes, nq * n * d: the filter's fixed cost (about 0.1 ms of small
+// launches) loses against a few scans of a small shard.  The default is the
+// smallest measured work from which the image path won at every point of
+// tools/qu8_batch_sweep.py at or above it (profiles/qu8_batch_sweep.json: 16
+// queries over 100 k x 128, 0.124 vs 0.130 ms; lost at 2 queries over
+// 100 k x 768, 0.127 vs 0.073 ms; 10M x 768: 1.27 / 1.33 / 1.39 / 2.67 ms for
+// 2 / 16 / 64 / 256 queries against 2.4 / 18.4 / 72.5 / 289 ms).
+static bool use_batched_qu8(int64_t nq, int64_t d, bool aligned, int64_t n, bool img8, int64_t k) {
+  const int64_t min_q = option(kOptBatchMinQ) >= 2 ? option(kOptBatchMinQ) : 2;
+  if (!img8 || !use_filter() || nq < min_q || !aligned || d % 16 != 0 || k > i8_max_k())
+    return false;
+  return (double)nq * (double)n * (double)d >= (double)option(kOptQu8BatchMinWork);
+}
+
 static bool use_batched(int64_t nq, int dtype, int64_t d, bool aligned, int64_t n, bool img8,
                         int64_t k) {
   if (option(kOptBatched) == 0) return false;
+  if (dtype == FX_DTYPE_QU8) return use_batched_qu8(nq, d, aligned, n, img8, k);
   // 2 queries: 6.5 ms vs 2 x 4.5 ms (10Mx768); "batch_min_queries" = 1 also
   // sends every single query through the filter
   int64_t min_q = option(kOptBatchMinQ) >= 1 ? option(kOptBatchMinQ) : 2;
@@ -198,6 +228,9 @@ static int plan_batched(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, 
     b->off_topr = off;
     off += align256((size_t)nq * k * 8);
   }
+  // quint8: the L2 scan's transformed queries (launch_qu8_query)
+  b->off_qt = off;
+  if (dtype == FX_DTYPE_QU8) off += align256((size_t)nq * d * 4);
   // the selects' prune scratch (int8 plans at large k): the slice count is
   // fixed here, once, and every select of this plan is launched with it
   b->prune_lists = b->img8 ? select_prune_lists(k, b->cap) : 0;
@@ -284,9 +317,7 @@ int plan_search(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, int metr
   if (rc) return rc;
   const size_t single_total = s->total;
   rc = plan_batched(n, d, dtype, nq, k,
-                    img8 && k <= i8_max_k() && d % 8 == 0 &&
-                        (dtype == FX_DTYPE_F32 || dtype == FX_DTYPE_F16),
-                    &s->batch);
+                    img8 && k <= i8_max_k() && d % 8 == 0, &s->batch);
   if (rc) return rc;
   s->batched = true;
   s->fb_queries = fq;

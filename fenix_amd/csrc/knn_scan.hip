@@ -1053,13 +1053,24 @@ int plan_scan(int64_t n, int64_t d, int dtype, int64_t k, int metric, bool align
   p->qbytes = qbytes;
   p->smem = smem;
   int cus = 0, occ = 0;
-  int rc = device_cus(&cus);
-  if (rc) return rc;
-  // (the streaming kernel needs fewer registers than the tiles: its own limit)
-  rc = kernel_occupancy((const void*)(p->fn_stream != nullptr ? p->fn_stream : p->fn), 256, smem,
-                        &occ);
-  if (rc) return rc;
-  if (p->fn_dma != nullptr) {  // one grid serves both variants: the smaller occupancy
+  // A host without a GPU can still plan (workspace sizes, which path a shape
+  // takes: capacity planning, the CPU tests): it is answered for the build's
+  // target, an MI355X's 256 CUs at the occupancy cap below.  Nothing launches
+  // there.
+  const bool device = device_present();
+  int rc = FX_OK;
+  if (device) {
+    rc = device_cus(&cus);
+    if (rc) return rc;
+    // (the streaming kernel needs fewer registers than the tiles: its own limit)
+    rc = kernel_occupancy((const void*)(p->fn_stream != nullptr ? p->fn_stream : p->fn), 256, smem,
+                          &occ);
+    if (rc) return rc;
+  } else {
+    cus = 256;
+    occ = 1 << 20;
+  }
+  if (device && p->fn_dma != nullptr) {  // one grid serves both variants: the smaller occupancy
     int occ2 = 0;
     // the DMA variants may take more than the default 64 KB of dynamic LDS
     rc = allow_lds((const void*)p->fn_dma);

@@ -445,7 +445,8 @@ class Engine:
 
     def filter_image(self, shard: Shard, nq: int, k: int, metric: int, build: bool = True
                      ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], int]:
-        """The filter image of an f32 (or, int8 images, f16) shard for a search that runs the batched
+        """The filter image of an f32 (or, int8 images, f16 or quint8) shard for a
+        search that runs the batched
         filter (fx_filter_image_used): (image, rowinfo, bits), bits 8
         (fx_filter_image8, the default) or 16 (fx_filter_image) as the library
         option "filter_image" says, built on first use and kept while the
@@ -468,9 +469,8 @@ class Engine:
         cannot hand its memory to another allocation early."""
         none = (None, None, 0)
         bits = _lib.get_option("filter_image")
-        # int8 images serve f32 and f16 corpora, fp16 images f32 ones
-        if ((shard.dtype_id != _lib.DTYPE_F32
-             and not (bits == 8 and shard.dtype_id == _lib.DTYPE_F16)) or bits not in (8, 16)
+        # int8 images serve f32, f16 and quint8 corpora, fp16 images f32 ones
+        if ((shard.dtype_id != _lib.DTYPE_F32 and bits != 8) or bits not in (8, 16)
                 or not _lib.filter_image_used(shard.n, shard.d, shard.dtype_id, nq, k, metric)):
             return none
         t = shard.data
@@ -480,7 +480,8 @@ class Engine:
             return none
         key = id(t)
         rkey = ("image", self.device.index, key)
-        sig = (t.data_ptr(), tuple(t.shape), t._version, bits)
+        # (a quint8 image holds the dequantised rows: scale and zero point too)
+        sig = (t.data_ptr(), tuple(t.shape), t._version, bits, shard.scale, shard.zero_point)
         hit = self._images.get(key)
         if hit is not None and hit[0] == sig:
             RESIDENT.touch(rkey)
@@ -510,8 +511,9 @@ class Engine:
         except torch.cuda.OutOfMemoryError:
             return none  # the f32 filter (no image) is always correct
         if bits == 8:
-            _lib.check(L.fx_filter_image8_typed(_ptr(t), shard.dtype_id, n, d, _ptr(img),
-                                                _ptr(info), self._stream()))
+            c = shard.corpus()
+            _lib.check(L.fx_filter_image8_ex(ctypes.byref(c), _ptr(img), _ptr(info),
+                                             self._stream()))
         else:
             _lib.check(L.fx_filter_image(_ptr(t), n, d, _ptr(img), _ptr(info), self._stream()))
         ev = torch.cuda.Event()
@@ -541,10 +543,21 @@ class Engine:
                      out_row: torch.Tensor) -> None:
         """fx_knn_search on one shard.  queries [nq, D] f32 on device; caller holds lock."""
         nq = queries.shape[0]
-        if shard.dtype_id == _lib.DTYPE_QU8:
-            self._search_ex(shard, None, -1, queries, metric, k, mask, out_dist, out_row)
-            return
         img, info, bits = self.filter_image(shard, nq, k, metric)
+        if shard.dtype_id == _lib.DTYPE_QU8:
+            # quint8 codes: a batch the library plans on an int8 image
+            # (fx_filter_image_used) and whose image is held goes through it,
+            # everything else through the exact scan
+            if img is None:
+                self._search_ex(shard, None, -1, queries, metric, k, mask, out_dist, out_row)
+                return
+            c = shard.corpus()
+            ws = self._workspace(_lib.knn_workspace_bytes(shard.n, shard.d, shard.dtype_id, nq, k))
+            self._hold(shard.data)
+            _lib.check(_lib.load().fx_knn_search_img8_ex(
+                ctypes.byref(c), _ptr(img), _ptr(info), _ptr(queries), nq, metric, k, _ptr(mask),
+                _ptr(ws), ws.numel(), _ptr(out_dist), _ptr(out_row), self._stream()))
+            return
         ws = self._workspace(_lib.knn_workspace_bytes(shard.n, shard.d, shard.dtype_id, nq, k,
                                                       img8=bits == 8))
         self._hold(shard.data)
@@ -592,6 +605,12 @@ class Engine:
                                                       img8=bits == 8))
         self._hold(shard.data)
         L = _lib.load()
+        if shard.dtype_id == _lib.DTYPE_QU8:  # (bits 0: no image, the exact scan's lists)
+            c = shard.corpus()
+            _lib.check(L.fx_knn_scan_img8_ex(
+                ctypes.byref(c), _ptr(img), _ptr(info), _ptr(queries), nq, metric, k, _ptr(mask),
+                _ptr(ws), ws.numel(), self._stream()))
+            return ScanState(ws, img, info, bits)
         _lib.check(
             (L.fx_knn_scan_img8 if bits == 8 else L.fx_knn_scan_img)(
                 _ptr(shard.data), shard.dtype_id, shard.n, shard.d, shard.row_base,
@@ -611,6 +630,12 @@ class Engine:
         nq = queries.shape[0]
         ws = state.ws
         L = _lib.load()
+        if shard.dtype_id == _lib.DTYPE_QU8:
+            c = shard.corpus()
+            _lib.check(L.fx_knn_reduce_img8_ex(
+                ctypes.byref(c), _ptr(state.image), _ptr(queries), nq, metric, k, _ptr(mask),
+                _ptr(ws), ws.numel(), _ptr(out_dist), _ptr(out_row), self._stream()))
+            return
         if state.bits == 8 and state.image is not None:
             _lib.check(L.fx_knn_reduce_img8(
                 _ptr(shard.data), shard.dtype_id, shard.n, shard.d, shard.row_base,

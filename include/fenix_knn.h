@@ -44,7 +44,10 @@ extern "C" {
 #define FX_DTYPE_F16 1
 #define FX_DTYPE_QU8 2     /* uint8 codes, value = scale * (code - zero_point):
                               the quint8 tensor column of ex/arrow/quint8/quint8.py:56-145;
-                              fx_knn_*_ex entry points only */
+                              the entry points that take an fx_corpus (*_ex) only;
+                              the shape-only planning calls (fx_filter_image_used,
+                              fx_knn_workspace_bytes*, fx_knn_filter_counts / _state)
+                              accept it too */
 
 /* metric; aliases are resolved by the host (coder.py:39 "euclidean"->l2,
  * coder.py:47 "dot"->inner_product) */
@@ -78,6 +81,11 @@ int fx_device_count(int* out);
  *                            corpora: 8 (fx_filter_image8), 16
  *                            (fx_filter_image) or 0 (none); read by the host
  *                            (fenix_amd.engine), not by the library's calls
+ *   "qu8_batch_min_work" 204800000  a batch over quint8 codes goes through a
+ *                            supplied int8 filter image from nq * n * d code
+ *                            bytes on; below, each query runs the exact scan
+ *                            (0: every batch of >= 2 queries the image serves;
+ *                            the default: profiles/qu8_batch_sweep.json)
  * Test switches (they change which code runs, never the results):
  *   "batch_cap"           0  candidate buffer per query of the batched filter
  *                            (0: max(64 k, 16 K); smaller than 16 k is ignored)
@@ -451,6 +459,35 @@ typedef struct fx_corpus {
  * shard.  k <= fx_max_k().  Exact scan only (a caller with a filter image
  * keeps the per-shard calls).  Results equal the per-shard form bit for bit.
  */
+/*
+ * The int8 filter image through the descriptor: fx_filter_image8_ex =
+ * fx_filter_image8_typed for float32 / float16 rows, and for FX_DTYPE_QU8
+ * codes (d a multiple of 16) the same fragment-ordered, row-permuted image
+ * and the same rowinfo [n][4] of the rows scale * (code - zero_point), the
+ * row terms taken from the integers code - zero_point (sizes:
+ * fx_filter_image8_bytes).  fx_knn_scan_img8_ex / fx_knn_reduce_img8_ex /
+ * fx_knn_search_img8_ex = fx_knn_scan_img8 / fx_knn_reduce_img8 /
+ * fx_knn_search_img8 on the descriptor (no row list).  With an image, a batch
+ * of >= 2 queries over quint8 codes (d % 16 == 0, 16-B aligned, k <= option
+ * "i8_max_k", nq * n * d >= option "qu8_batch_min_work") runs the int8 filter
+ * over the image and rescores its candidates from the codes in the quint8
+ * scan's own arithmetic: rows and distance bits equal nq single-query
+ * fx_knn_search_ex calls.  Every other quint8 search (a single query, image
+ * NULL, k or shape outside the gate) runs the exact scan of fx_knn_search_ex.
+ * Workspace: fx_knn_workspace_bytes_img8 with dtype FX_DTYPE_QU8.
+ */
+int fx_filter_image8_ex(const fx_corpus* c, void* image, float* rowinfo, void* stream);
+int fx_knn_scan_img8_ex(const fx_corpus* c, const void* image, const float* rowinfo,
+                        const float* queries, int64_t nq, int metric, int64_t k,
+                        const uint32_t* mask, void* ws, size_t ws_bytes, void* stream);
+int fx_knn_reduce_img8_ex(const fx_corpus* c, const void* image, const float* queries, int64_t nq,
+                          int metric, int64_t k, const uint32_t* mask, void* ws, size_t ws_bytes,
+                          float* out_dist, int64_t* out_row, void* stream);
+int fx_knn_search_img8_ex(const fx_corpus* c, const void* image, const float* rowinfo,
+                          const float* queries, int64_t nq, int metric, int64_t k,
+                          const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
+                          int64_t* out_row, void* stream);
+
 int fx_knn_search_shards_workspace_bytes(const fx_corpus* shards, int nshards, int64_t nq,
                                          int64_t k, size_t* out_bytes);
 int fx_knn_search_shards(const fx_corpus* shards, int nshards, const float* queries, int64_t nq,

@@ -4,6 +4,7 @@ means a kernel read data that had not landed).  Prints one line per case.
 
     python tools/race_check.py [--reps 30] [--nq 1,2,16,64,65,256] [--img6 0,1,2]
     FENIX_AMD_LIB=fenix_amd/lib/libfenix_knn_pe0.so python tools/race_check.py ...
+    python tools/race_check.py --qu8 --reps 40 --nq 64,65,256 --d 768   (quint8 codes)
 """
 import argparse
 import os
@@ -29,6 +30,9 @@ p.add_argument("--n", type=int, default=70_000,
                help="rows (600000 and up: a 3-phase plan, every int8 phase in the batched kernels)")
 p.add_argument("--fp16", action="store_true",
                help="the fp16 filter kernels instead: fp16 image (k = 30) and no image (k = 300)")
+p.add_argument("--qu8", action="store_true",
+               help="a quint8 corpus (codes 64 + 40 N(0, 1), scale 1e-3; d % 16 == 0, nq >= 2): "
+                    "the same kernels over image8_qu8_kernel's image, quint8 rescoring")
 a = p.parse_args()
 eng = Engine.get(torch.device("cuda", 0))
 k = 30
@@ -57,21 +61,30 @@ if a.fp16:
                              f"{moved} of {a.reps - 1} repetitions moved"), flush=True)
     sys.exit(0)
 for n, d in [(a.n, int(v)) for v in a.d.split(",")]:
-    xh = _extreme_rows(n, d, 49)
-    x = torch.from_numpy(xh).to(eng.device)
+    if a.qu8:
+        xh = np.clip(np.rint(64 + 40.0 * O.fill_normal(n, d, seed=49)), 0, 255).astype(np.uint8)
+        shard = Shard(torch.from_numpy(xh).to(eng.device), 0, 1e-3, 64)
+    else:
+        xh = _extreme_rows(n, d, 49)
+        shard = Shard(torch.from_numpy(xh).to(eng.device), 0)
     eng.clear_images()
     mask = device_mask(np.random.RandomState(4).rand(n) < 0.8, eng.device)
     for nq in [int(v) for v in a.nq.split(",")]:
         q = torch.from_numpy(O.fill_normal(nq, d, seed=60 + nq)).to(eng.device)
+        if a.qu8:
+            q = q * 0.04  # (the rows' magnitude: scale * 40)
         for msk in (None, mask):
             first = None
             for img6, img8 in [(int(v), int(w)) for v in a.img6.split(",") for w in a.img8.split(",")]:
-                with _lib.options(img6=img6, img8=img8, filter_image=8, batch_min_queries=1):
+                with _lib.options(img6=img6, img8=img8, filter_image=8, batch_min_queries=1,
+                                  qu8_batch_min_work=0):
                     ref = None
                     moved = 0
                     for _ in range(a.reps):
-                        st = eng.scan(Shard(x, 0), q, a.metric, k, msk)
-                        c, _cap = eng.filter_counts(Shard(x, 0), nq, a.metric, k, st)
+                        st = eng.scan(shard, q, a.metric, k, msk)
+                        c, _cap = eng.filter_counts(shard, nq, a.metric, k, st)
+                        if c is None:
+                            break
                         if ref is None:
                             ref = c
                         elif not np.array_equal(c, ref):
@@ -85,6 +98,9 @@ for n, d in [(a.n, int(v)) for v in a.d.split(",")]:
                         first = ref
                     else:
                         same = bool(np.array_equal(ref, first))
+                    if ref is None:
+                        print(f"d {d} nq {nq}: no filter", flush=True)
+                        continue
                     print(f"d {d} nq {nq} mask {msk is not None} img6 {img6} img8 {img8}: {moved} of "
                           f"{a.reps - 1} repetitions moved"
                           + ("" if same is None else f"; counts equal the first variant's: {same}"),
