@@ -57,9 +57,9 @@ static int fallback_search(const SearchLayout& s, const fx_corpus& c, const floa
   return FX_OK;
 }
 
-// fp16 filter phases (knn_filter.hip).  Sampling phases append the UPPER
-// bound of every row whose lower bound reaches the threshold; the k-th upper
-// bound of any row subset bounds the global k-th distance from above, so it is
+// fp16 filter phases (knn_filter.hip; the rescoring: knn_exact.hip).
+// Sampling phases append the UPPER bound of every row whose lower bound
+// reaches the threshold; the k-th upper bound of any row subset bounds the global k-th distance from above, so it is
 // the next phase's threshold.  The final phase (every row) appends lower and
 // upper bounds; the k-th upper bound among its candidates is a tighter
 // threshold, and only candidates whose lower bound reaches it are rescored
@@ -68,39 +68,35 @@ static int fallback_search(const SearchLayout& s, const fx_corpus& c, const floa
 // With an fp16 filter image of an f32 corpus (fx_filter_image) the phases
 // stream the image (half the bytes) and the rescoring reads the f32 rows.
 // (An int8 filter image has phases of its own: filter_phases_i8.)
-static int filter_phases(const BatchLayout& b, const void* X, int dtype, const void* image,
-                         const float* rowinfo, int64_t n, int64_t d, int64_t row_base,
-                         const float* Q, int64_t nq, int metric, int64_t k,
-                         const uint32_t* mask, char* w, hipStream_t st) {
-  float* qnorm = reinterpret_cast<float*>(w + b.off_qnorm);
-  uint64_t* thr = reinterpret_cast<uint64_t*>(w + b.off_thr);
-  uint32_t* count = reinterpret_cast<uint32_t*>(w + b.off_count);
-  uint64_t* cand = reinterpret_cast<uint64_t*>(w + b.off_cand);
-  uint64_t* cand_ub = reinterpret_cast<uint64_t*>(w + b.off_cand_ub);
-  uint16_t* qh = reinterpret_cast<uint16_t*>(w + b.off_qh);
-  float* qinfo = reinterpret_cast<float*>(w + b.off_qinfo);
-  int rc = launch_qprep(Q, nq, b.nq_pad, (int)d, b.dq, metric, qh, qinfo, st);
+static int filter_phases(const BatchLayout& b, const fx_corpus& c, const void* image,
+                         const float* rowinfo, const float* Q, int64_t nq, int metric, int64_t k,
+                         const uint32_t* mask, void* ws, hipStream_t st) {
+  const BatchWorkspace w(b, ws);
+  const ExactSource src = {c.data, c.dtype, c.n, (int)c.d, c.row_base, Q, w.qnorm, metric, Quant()};
+  uint16_t* qh = reinterpret_cast<uint16_t*>(w.qh);
+  int rc = launch_qprep(Q, nq, b.nq_pad, src.d, b.dq, metric, qh, w.qinfo, st);
   if (rc) return rc;
   if (metric == FX_METRIC_COS) {  // the scan's max(|q|, 1e-12) for the rescoring
-    rc = launch_qnorm(Q, nq, (int)d, qnorm, st, 0);
+    rc = launch_qnorm(Q, nq, src.d, w.qnorm, st);
     if (rc) return rc;
   }
-  hipError_t e = hipMemsetAsync(thr, 0xFF, (size_t)nq * 8, st);
+  hipError_t e = hipMemsetAsync(w.thr, 0xFF, (size_t)nq * 8, st);
   // a one-level threshold merge resets the counts it read, so only the first
   // phase needs a fill (each fill is a ~5 us launch)
   const bool merge_zeroes = b.merge.levels == 1;
   for (int ph = 0; ph < b.nphases && e == hipSuccess; ++ph) {
     const bool last = ph + 1 == b.nphases;
     // (the lists are read up to count only: no fill of the candidate buffers)
-    if (ph == 0 || !merge_zeroes) e = hipMemsetAsync(count, 0, (size_t)nq * 4 * kCountStride, st);
+    if (ph == 0 || !merge_zeroes)
+      e = hipMemsetAsync(w.count, 0, (size_t)nq * 4 * kCountStride, st);
     if (e != hipSuccess) break;
     FilterArgs a = {};
-    a.X = image != nullptr ? image : X;
-    a.dtype = image != nullptr ? FX_DTYPE_F16 : dtype;
+    a.X = image != nullptr ? image : c.data;
+    a.dtype = image != nullptr ? FX_DTYPE_F16 : c.dtype;
     a.rowinfo = image != nullptr ? rowinfo : nullptr;
-    a.n = n;
-    a.d = (int)d;
-    a.row_base = row_base;
+    a.n = c.n;
+    a.d = src.d;
+    a.row_base = c.row_base;
     a.Qh = qh;
     a.dq = b.dq;
     a.qstride = b.nq_pad;
@@ -110,16 +106,16 @@ static int filter_phases(const BatchLayout& b, const void* X, int dtype, const v
     // with upper bounds at or below it, so no row whose upper bound exceeds
     // it is among them (option "batch_ub_test" = 0: the lower-bound test)
     a.ub_test = ph > 0 && !last && option(kOptBatchUbTest) != 0 ? 1 : 0;
-    a.qinfo = qinfo;
+    a.qinfo = w.qinfo;
     a.nq = nq;
     a.mask = mask;
     a.tile_start = b.start[ph];
     a.tile_stride = b.stride[ph];
     a.num_tiles = b.num[ph];
-    a.thr = thr;
-    a.count = count;
-    a.cand = cand;
-    a.cand_ub = last ? cand_ub : nullptr;
+    a.thr = w.thr;
+    a.count = w.count;
+    a.cand = w.cand;
+    a.cand_ub = last ? w.cand_ub : nullptr;
     a.cap = (int)b.cap;
     a.diag = diag_env("FX_FILTER_DIAG", 0);
     rc = launch_filter(a, metric, st);
@@ -128,16 +124,15 @@ static int filter_phases(const BatchLayout& b, const void* X, int dtype, const v
     // the threshold it tested against stay in the workspace
     if (last && option(kOptFilterHold) != 0) return FX_OK;
     // the k-th upper bound of this phase's candidates: next threshold
-    rc = run_merge(b.merge, last ? cand_ub : cand, nq, k, w + b.off_merge, nullptr, nullptr, st,
-                   thr, nullptr, 0, count, !last);
+    rc = run_merge(b.merge, last ? w.cand_ub : w.cand, nq, k, w.merge, nullptr, nullptr, st,
+                   w.thr, nullptr, 0, w.count, !last);
     if (rc) return rc;
   }
   if (e != hipSuccess) {
     set_error("batched memset: %s", hipGetErrorString(e));
     return FX_EHIP;
   }
-  return launch_rescore(X, dtype, n, (int)d, row_base, Q, qnorm, nq, count, cand, (int)b.cap,
-                        metric, thr, st);
+  return launch_rescore(src, nq, w.count, w.cand, (int)b.cap, w.thr, st);
 }
 
 // The int8 image's phases (fx_filter_image8; rows in image8_perm order, so
@@ -169,32 +164,27 @@ static int filter_phases(const BatchLayout& b, const void* X, int dtype, const v
 // image8_qu8_kernel, knn_filter.hip).  IP and cosine take the queries as they are.
 static constexpr int64_t kI8RescoreAllMaxQ = 2;
 
-static int filter_phases_i8(const BatchLayout& b, const void* X, int dtype, const void* image,
-                            const float* rowinfo, int64_t n, int64_t d, int64_t row_base,
-                            const float* Q, int64_t nq, int metric, int64_t k,
-                            const uint32_t* mask, char* w, hipStream_t st, Quant z) {
-  float* qnorm = reinterpret_cast<float*>(w + b.off_qnorm);
-  uint64_t* thr = reinterpret_cast<uint64_t*>(w + b.off_thr);
-  uint32_t* count = reinterpret_cast<uint32_t*>(w + b.off_count);
-  uint64_t* cand = reinterpret_cast<uint64_t*>(w + b.off_cand);
-  uint64_t* cand_ub = reinterpret_cast<uint64_t*>(w + b.off_cand_ub);
+static int filter_phases_i8(const BatchLayout& b, const fx_corpus& c, const void* image,
+                            const float* rowinfo, const float* Q, int64_t nq, int metric,
+                            int64_t k, const uint32_t* mask, void* ws, hipStream_t st) {
+  const BatchWorkspace w(b, ws);
+  const Quant z = {c.scale, (float)c.zero_point};
+  const int d = (int)c.d;
   const int64_t nq_pad8 = (nq + 255) / 256 * 256;
   int rc;
-  const bool qu8_l2 = dtype == FX_DTYPE_QU8 && metric == FX_METRIC_L2;
+  const bool qu8_l2 = c.dtype == FX_DTYPE_QU8 && metric == FX_METRIC_L2;
   if (qu8_l2) {  // from here on Q is the quint8 scan's q' (L2 needs no |q|)
-    float* qt = reinterpret_cast<float*>(w + b.off_qt);
-    rc = launch_qu8_query(Q, nq, (int)d, z, qt, st);
+    rc = launch_qu8_query(Q, nq, d, z, w.qt, st);
     if (rc) return rc;
-    Q = qt;
+    Q = w.qt;
   }
+  const ExactSource src = {c.data, c.dtype, c.n, d, c.row_base, Q, w.qnorm, metric, z};
   // (the query prep also empties thr and zeroes the counts)
-  rc = launch_qprep8(Q, nq, nq_pad8, (int)d, b.dq, metric,
-                     reinterpret_cast<int8_t*>(w + b.off_qh),
-                     reinterpret_cast<float*>(w + b.off_qinfo), st, thr, count,
-                     qu8_l2 ? &z : nullptr);
+  rc = launch_qprep8(Q, nq, nq_pad8, d, b.dq, metric, reinterpret_cast<int8_t*>(w.qh), w.qinfo,
+                     st, w.thr, w.count, qu8_l2 ? &z : nullptr);
   if (rc) return rc;
   if (metric == FX_METRIC_COS) {  // the scan's max(|q|, 1e-12) for the exact distances
-    rc = launch_qnorm(Q, nq, (int)d, qnorm, st, 0);
+    rc = launch_qnorm(Q, nq, d, w.qnorm, st);
     if (rc) return rc;
   }
   auto args = [&](int ph) {
@@ -202,36 +192,32 @@ static int filter_phases_i8(const BatchLayout& b, const void* X, int dtype, cons
     a.X = image;
     a.dtype = FX_DTYPE_F16;
     a.rowinfo = rowinfo;
-    a.n = n;
-    a.d = (int)d;
-    a.row_base = row_base;
-    a.Qh = reinterpret_cast<const uint16_t*>(w + b.off_qh);
+    a.n = c.n;
+    a.d = d;
+    a.row_base = c.row_base;
+    a.Qh = reinterpret_cast<const uint16_t*>(w.qh);
     a.dq = b.dq;
     a.qstride = nq_pad8;
     a.img8 = 1;
-    a.perm_a = image8_perm(n);
-    a.qinfo = reinterpret_cast<const float*>(w + b.off_qinfo);
+    a.perm_a = image8_perm(c.n);
+    a.qinfo = w.qinfo;
     a.nq = nq;
     a.mask = mask;
     a.tile_start = b.start[ph];
     a.tile_stride = b.stride[ph];
     a.num_tiles = b.num[ph];
-    a.thr = thr;
-    a.count = count;
-    a.cand = cand;
+    a.thr = w.thr;
+    a.count = w.count;
+    a.cand = w.cand;
     a.cap = (int)b.cap;
     a.diag = diag_env("FX_FILTER_DIAG", 0);
     return a;
   };
   // the exact k-th of the k best upper bounds in `keys` -> thr (one fused
   // launch when the buffer fits one workgroup's LDS)
-  uint64_t* prune = reinterpret_cast<uint64_t*>(w + b.off_prune);
-  int64_t* topr = reinterpret_cast<int64_t*>(w + b.off_topr);
-  auto exact_threshold = [&](const uint64_t* keys, bool zero, const uint64_t* gate = nullptr,
-                             int64_t gate_num = 0, int64_t gate_den = 1) {
-    return launch_exact_threshold(X, dtype, n, (int)d, row_base, Q, qnorm, nq, keys, b.cap, count,
-                                  zero, (int)k, metric, thr, st, prune, b.prune_lists, topr, gate,
-                                  gate_num, gate_den, z);
+  auto exact_threshold = [&](const uint64_t* keys, bool zero, OverflowGate gate = OverflowGate()) {
+    return launch_exact_threshold(src, nq, keys, b.cap, w.count, zero, (int)k, w.thr, w.prune,
+                                  w.topr, gate, st);
   };
   const int m = b.nphases;
   for (int ph = 0; ph + 2 < m; ++ph) {  // sampling phases: thresholds only
@@ -241,15 +227,15 @@ static int filter_phases_i8(const BatchLayout& b, const void* X, int dtype, cons
     rc = launch_filter(a, metric, st);
     if (rc) return rc;
     // (both reset the counts they read: the next phase appends from 0)
-    rc = ph + 3 == m ? exact_threshold(cand, true)
-                     : launch_sample_threshold(cand, nq, b.cap, count, true, (int)k, thr, st,
-                                               prune, b.prune_lists);
+    rc = ph + 3 == m ? exact_threshold(w.cand, true)
+                     : launch_sample_threshold(w.cand, nq, b.cap, w.count, true, (int)k, w.thr,
+                                               w.prune, st);
     if (rc) return rc;
   }
   // F1: the last sample's tiles (with one phase: every tile), both bounds
   FilterArgs f1 = args(m >= 2 ? m - 2 : 0);
   f1.all_pass = m <= 2 ? 1 : 0;
-  f1.cand_ub = cand_ub;
+  f1.cand_ub = w.cand_ub;
   rc = launch_filter(f1, metric, st);
   if (rc) return rc;
   // option "filter_hold" (test switch): return after the last filter pass, its
@@ -260,14 +246,15 @@ static int filter_phases_i8(const BatchLayout& b, const void* X, int dtype, cons
     if (hold && t2 <= 0) return FX_OK;
     // F1's threshold, then (t2 > 0) the overflow gate on it (launch_overflow_gate's
     // prediction, run by the select's own workgroups)
-    rc = t2 > 0 ? exact_threshold(cand_ub, false, cand, t2, t1) : exact_threshold(cand_ub, false);
+    rc = t2 > 0 ? exact_threshold(w.cand_ub, false, OverflowGate{w.cand, t2, t1})
+                : exact_threshold(w.cand_ub, false);
     if (rc) return rc;
     if (t2 > 0) {
       // F2: the tiles after F1's prefix
       FilterArgs f2 = args(m - 1);
       f2.tile_start = t1;
       f2.num_tiles = t2;
-      f2.cand_ub = cand_ub;
+      f2.cand_ub = w.cand_ub;
       f2.skip_full = 1;
       rc = launch_filter(f2, metric, st);
       if (rc) return rc;
@@ -278,69 +265,11 @@ static int filter_phases_i8(const BatchLayout& b, const void* X, int dtype, cons
   // rescore every candidate under F1's threshold instead (a few thousand 3 KB
   // rows, ~3-6 us spread over the chip, against a ~25 us one-workgroup select)
   if (m < 2 || nq > kI8RescoreAllMaxQ) {
-    rc = exact_threshold(cand_ub, false);
+    rc = exact_threshold(w.cand_ub, false);
     if (rc) return rc;
   }
-  return launch_rescore(X, dtype, n, (int)d, row_base, Q, qnorm, nq, count, cand, (int)b.cap,
-                        metric, thr, st, z);
+  return launch_rescore(src, nq, w.count, w.cand, (int)b.cap, w.thr, st);
 }
-
-#ifdef FX_DIAG_BUILD
-static int batched_phases(const BatchLayout& b, const float* X, int64_t n, int64_t d,
-                          int64_t row_base, const float* Q, int64_t nq, int metric, int64_t k,
-                          const uint32_t* mask, char* w, hipStream_t st) {
-  float* qnorm = reinterpret_cast<float*>(w + b.off_qnorm);
-  uint64_t* thr = reinterpret_cast<uint64_t*>(w + b.off_thr);
-  uint32_t* count = reinterpret_cast<uint32_t*>(w + b.off_count);
-  uint64_t* cand = reinterpret_cast<uint64_t*>(w + b.off_cand);
-  const bool l2 = metric == FX_METRIC_L2;
-  int rc = launch_qnorm(Q, nq, (int)d, qnorm, st, l2 ? 1 : 0);
-  if (rc) return rc;
-  // fp32 error bound of |x|^2 + |q|^2 - 2 x.q relative to |x|^2 + |q|^2:
-  // 2 gamma_d for the three d-term sums + a few roundings, with 25 % slack
-  const float l2_eps = (float)((2.0 * (double)d + 8.0) * 5.9604644775390625e-08 * 1.25);
-  hipError_t e = hipMemsetAsync(thr, 0xFF, (size_t)nq * 8, st);
-  for (int ph = 0; ph < b.nphases && e == hipSuccess; ++ph) {
-    e = hipMemsetAsync(count, 0, (size_t)nq * 4 * kCountStride, st);
-    if (e == hipSuccess) e = hipMemsetAsync(cand, 0xFF, (size_t)nq * b.cap * 8, st);
-    if (e != hipSuccess) break;
-    BatchArgs a = {};
-    a.X = X;
-    a.n = n;
-    a.d = (int)d;
-    a.row_base = row_base;
-    a.Q = Q;
-    a.qnorm = qnorm;
-    a.nq = nq;
-    a.mask = mask;
-    a.tile_start = b.start[ph];
-    a.tile_stride = b.stride[ph];
-    a.num_tiles = b.num[ph];
-    a.thr = thr;
-    a.count = count;
-    a.cand = cand;
-    a.cap = (int)b.cap;
-    a.l2_eps = l2_eps;
-    rc = launch_batch(a, metric, st);
-    if (rc) return rc;
-    if (l2) {  // approximate keys -> exact distances before any select
-      rc = launch_rescore(X, FX_DTYPE_F32, n, (int)d, row_base, Q, nullptr, nq, count, cand,
-                          (int)b.cap, FX_METRIC_L2, nullptr, st);
-      if (rc) return rc;
-    }
-    if (ph + 1 < b.nphases) {
-      // the k-th composite of this sample bounds the global k-th from above
-      rc = run_merge(b.merge, cand, nq, k, w + b.off_merge, nullptr, nullptr, st, thr);
-      if (rc) return rc;
-    }
-  }
-  if (e != hipSuccess) {
-    set_error("batched memset: %s", hipGetErrorString(e));
-    return FX_EHIP;
-  }
-  return FX_OK;
-}
-#endif  // FX_DIAG_BUILD
 
 }  // namespace fx
 
@@ -429,10 +358,10 @@ static int search_layout(const fx_corpus& c, int64_t nq, int metric, int64_t k, 
 }
 
 // a filter image applies to rows of whole 16-B pieces (d % 8 == 0) through
-// the filter: an int8 image where the plan took it (BatchLayout::img8, f32 or
-// f16 rows), an fp16 image to f32 rows
+// the filter: an int8 image where the plan took it (BatchLayout::img8, any
+// dtype), an fp16 image to f32 rows
 static bool image_applies(const SearchLayout& s, const fx_corpus& c, bool img8) {
-  if (!s.batched || !s.batch.filter) return false;
+  if (!s.batched) return false;
   return img8 ? s.batch.img8 : c.d % 8 == 0 && c.dtype == FX_DTYPE_F32;
 }
 
@@ -448,30 +377,22 @@ static int scan_impl(const SearchLayout& s, const fx_corpus& c, const void* imag
               (long long)(c.row_base + c.n));
     return FX_EUNSUPPORTED;
   }
-  char* w = reinterpret_cast<char*>(ws);
   if (s.batched) {
-    if (s.batch.filter) {
-      const bool img = image != nullptr && image_applies(s, c, img8);
-      if (img && (rowinfo == nullptr || (uintptr_t)image % 16 != 0)) {
-        set_error("filter image: null row info or image not 16-byte aligned");
-        return FX_EINVAL;
-      }
-      if (img && img8)
-        return filter_phases_i8(s.batch, c.data, c.dtype, image, rowinfo, c.n, c.d, c.row_base,
-                                queries, nq, metric, k, mask, w, st,
-                                Quant{c.scale, (float)c.zero_point});
-      if (c.dtype == FX_DTYPE_QU8) {  // (unreachable: quint8 batches are planned on an image)
-        set_error("quint8 batch without an int8 filter image");
-        return FX_EINVAL;
-      }
-      return filter_phases(s.batch, c.data, c.dtype, img ? image : nullptr, rowinfo, c.n, c.d,
-                           c.row_base, queries, nq, metric, k, mask, w, st);
+    const bool img = image != nullptr && image_applies(s, c, img8);
+    if (img && (rowinfo == nullptr || (uintptr_t)image % 16 != 0)) {
+      set_error("filter image: null row info or image not 16-byte aligned");
+      return FX_EINVAL;
     }
-#ifdef FX_DIAG_BUILD
-    return batched_phases(s.batch, reinterpret_cast<const float*>(c.data), c.n, c.d, c.row_base,
-                          queries, nq, metric, k, mask, w, st);
-#endif
+    if (img && img8)
+      return filter_phases_i8(s.batch, c, image, rowinfo, queries, nq, metric, k, mask, ws, st);
+    if (c.dtype == FX_DTYPE_QU8) {  // (unreachable: quint8 batches are planned on an image)
+      set_error("quint8 batch without an int8 filter image");
+      return FX_EINVAL;
+    }
+    return filter_phases(s.batch, c, img ? image : nullptr, rowinfo, queries, nq, metric, k, mask,
+                         ws, st);
   }
+  char* w = reinterpret_cast<char*>(ws);
   if (s.large) {
     ScanArgs a = scan_args(s.scan, c, nullptr, 0, mask, 1, kModeDist);
     a.q = queries;
@@ -510,9 +431,7 @@ static int reduce_impl(const SearchLayout& s, const fx_corpus& c, const float* q
   }
   // batched: final select over the last phase's candidates
   const BatchLayout& b = s.batch;
-  const uint64_t* cand = reinterpret_cast<const uint64_t*>(w + b.off_cand);
-  uint32_t* count = reinterpret_cast<uint32_t*>(w + b.off_count);
-  uint64_t* prune = reinterpret_cast<uint64_t*>(w + b.off_prune);
+  const BatchWorkspace bw(b, ws);
   // queries whose candidates overflowed `cap` are recomputed exactly, gated
   // on the device ("force_fallback" (test switch): every query)
   const int64_t gate_cap = option(kOptForceFallback) != 0 ? -1 : b.cap;
@@ -521,19 +440,20 @@ static int reduce_impl(const SearchLayout& s, const fx_corpus& c, const float* q
     // one round: the gated scan's lists feed the final select of the
     // overflowing queries (no merge levels of their own)
     const uint64_t* lists = nullptr;
-    rc = fallback_scan(s, c, queries, nq, k, mask, count, gate_cap, w + s.single_off, st, &lists);
+    rc = fallback_scan(s, c, queries, nq, k, mask, bw.count, gate_cap, w + s.single_off, st,
+                       &lists);
     if (rc) return rc;
-    return launch_final_select(cand, nq, b.cap, count, (int)k, out_dist, out_row, lists,
-                               s.scan.nlists * k, gate_cap, st, prune, b.prune_lists);
+    return launch_final_select(bw.cand, nq, b.cap, bw.count, (int)k, out_dist, out_row, lists,
+                               s.scan.nlists * k, gate_cap, bw.prune, st);
   }
   // (the fallback gate reads the counts next: kept)
-  rc = b.img8 ? launch_final_select(cand, nq, b.cap, count, (int)k, out_dist, out_row, nullptr, 0,
-                                    0, st, prune, b.prune_lists)
-              : run_merge(b.merge, cand, nq, k, w + b.off_merge, out_dist, out_row, st, nullptr,
-                          nullptr, 0, count);
+  rc = b.img8 ? launch_final_select(bw.cand, nq, b.cap, bw.count, (int)k, out_dist, out_row,
+                                    nullptr, 0, 0, bw.prune, st)
+              : run_merge(b.merge, bw.cand, nq, k, bw.merge, out_dist, out_row, st, nullptr,
+                          nullptr, 0, bw.count);
   if (rc) return rc;
-  return fallback_search(s, c, queries, nq, k, mask, count, gate_cap, w + s.single_off, out_dist,
-                         out_row, st);
+  return fallback_search(s, c, queries, nq, k, mask, bw.count, gate_cap, w + s.single_off,
+                         out_dist, out_row, st);
 }
 
 // The reduce half of a search call (fx_knn_reduce*): its own plan, which
@@ -708,20 +628,19 @@ int fx_knn_filter_state(const void* corpus, int dtype, int64_t n, int64_t d, int
   int rc = search_layout(corpus_of(corpus, dtype, n, d, 0), nq, metric, k, img8 != 0, ws,
                          ws_bytes, &s, true);
   if (rc) return rc;
-  if (!s.batched || !s.batch.filter) {
+  if (!s.batched) {
     set_error("fx_knn_filter_state: the search did not run the filter");
     return FX_EINVAL;
   }
-  const char* w = reinterpret_cast<const char*>(ws);
+  const BatchWorkspace w(s.batch, const_cast<void*>(ws));  // (read only)
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t cb = (size_t)nq * s.batch.cap * 8;
   hipError_t e = hipSuccess;
-  if (out_thr) e = hipMemcpyAsync(out_thr, w + s.batch.off_thr, (size_t)nq * 8,
-                                  hipMemcpyDeviceToDevice, st);
+  if (out_thr) e = hipMemcpyAsync(out_thr, w.thr, (size_t)nq * 8, hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess && out_cand)
-    e = hipMemcpyAsync(out_cand, w + s.batch.off_cand, cb, hipMemcpyDeviceToDevice, st);
+    e = hipMemcpyAsync(out_cand, w.cand, cb, hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess && out_cand_ub)
-    e = hipMemcpyAsync(out_cand_ub, w + s.batch.off_cand_ub, cb, hipMemcpyDeviceToDevice, st);
+    e = hipMemcpyAsync(out_cand_ub, w.cand_ub, cb, hipMemcpyDeviceToDevice, st);
   if (e != hipSuccess) {
     set_error("fx_knn_filter_state: %s", hipGetErrorString(e));
     return FX_EHIP;
@@ -745,8 +664,8 @@ int fx_knn_filter_counts(const void* corpus, int dtype, int64_t n, int64_t d, in
     return FX_OK;
   }
   *out_cap = s.batch.cap;
-  const char* c = reinterpret_cast<const char*>(ws) + s.batch.off_count;
-  hipError_t e = hipMemcpy2DAsync(out_counts, 4, c, 4 * kCountStride, 4, (size_t)nq,
+  const BatchWorkspace w(s.batch, const_cast<void*>(ws));  // (read only)
+  hipError_t e = hipMemcpy2DAsync(out_counts, 4, w.count, 4 * kCountStride, 4, (size_t)nq,
                                   hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) {
     set_error("fx_knn_filter_counts: %s", hipGetErrorString(e));

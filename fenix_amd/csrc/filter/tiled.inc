@@ -61,7 +61,7 @@ __device__ __forceinline__ void lds_write3_u32(uint32_t* p, uint32_t x, uint32_t
 //   cos  I + omega R' - (N / s) (1 - 2T - 2c) N_q / s_q    >= 0   (N = max(|x|, 1e-12))
 //   L2   I + omega R' - (n^2 / s) / (2 s_q) - (1/s) (n_q^2 - T^2 (1 + 2^-20) / (1 - g2)) / (2 s_q) >= 0
 // c = 3 g + 16 u and g2 = 2 g + 8 u cover the scan's own roundings (u = 2^-24;
-// knn_batch.hip exact_distance16: dot and norms in f32, one division).  Each
+// fx_exact.h exact_distance16: dot and norms in f32, one division).  Each
 // per-query coefficient carries a relative slack >= 16 u (the roundings of the
 // products and sums of the test) and the test compares with 12582912 - 8.
 // The appends' [lb, ub] (i8_bounds) are evaluated in f32 from the same terms,

@@ -11,7 +11,7 @@ constexpr int kModeDist = 1;
 // Per-query append counters of the batched kernels sit 128 B apart: every
 // counter in its own cache line, so the L2 channels serialise fewer atomics.
 constexpr int kCountStride = 32;
-// largest k of the one-workgroup select_kernel (knn_batch.hip): its LDS holds a
+// largest k of the one-workgroup selects (knn_select.hip): their LDS holds a
 // 16 384-entry chunk plus the k kept so far rounded up to a power of two, which
 // fits the 160 KB of a CU up to 2 048; also the bound of option "i8_max_k"
 constexpr int kSelectMaxK = 2048;
@@ -149,85 +149,101 @@ int run_merge(const MergePlan& p, const uint64_t* in, int64_t nq, int64_t k, voi
               uint64_t* out_kth = nullptr, const uint32_t* gate = nullptr,
               int64_t gate_cap = 0, uint32_t* count = nullptr, bool zero_count = false);
 
-// Batched queries (knn_batch.hip): fp32 MFMA GEMM + threshold filter.
-struct BatchArgs {
-  const float* X;         // [n][d] f32 corpus shard
-  int64_t n;
-  int d;
-  int64_t row_base;
-  const float* Q;         // [nq][d]
-  const float* qnorm;     // [nq] max(|q|, 1e-12) (cosine) / sum q^2 (L2)
-  int64_t nq;
-  const uint32_t* mask;
-  int64_t tile_start, tile_stride, num_tiles;  // which 128-row tiles to scan
-  const uint64_t* thr;    // [nq] append rows whose composite <= thr
-  uint32_t* count;        // [nq * kCountStride] appends (may exceed cap: overflow)
-  uint64_t* cand;         // [nq][cap]
-  int cap;
-  float l2_eps;           // L2: relative error bound of |x|^2+|q|^2-2x.q in fp32
-};
-int launch_batch(const BatchArgs& a, int metric, hipStream_t stream);
 // FX_DTYPE_QU8 rows: value = scale * (code - shift), as ScanArgs::qscale / qshift
 // (f32 / f16 rows: unused)
 struct Quant {
   float scale = 1.f, shift = 0.f;
 };
+
+// gridDim.y holds at most 65 535 queries: f(q0, qn) launches queries
+// [q0, q0 + qn) of a batch, chunk by chunk, until one fails
+template <typename F>
+int for_query_chunks(int64_t nq, F&& f) {
+  for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
+    if (int rc = f(q0, (nq - q0) < 65535 ? (nq - q0) : 65535)) return rc;
+  }
+  return FX_OK;
+}
+
+// Where the exact distances of a batched search come from: the corpus shard
+// and the queries as the single-query scan would read them.  The phase
+// drivers (capi.hip) build it once; the rescoring launchers (knn_exact.hip)
+// and the exact-threshold select (knn_select.hip) take it.
+struct ExactSource {
+  const void* X;       // [n][d] rows of dtype, whole 16-B slots (quint8: d % 16 == 0)
+  int dtype;
+  int64_t n;
+  int d;
+  int64_t row_base;    // global row of local row 0
+  const float* Q;      // [nq][d] the queries as the scan keeps them in LDS: for quint8
+                       // L2 launch_qu8_query's q', the queries themselves otherwise
+  const float* qnorm;  // [nq] max(|q|, 1e-12) as the scan computes it (read for cosine only)
+  int metric;
+  Quant z;             // quint8: the corpus's scale and zero point
+  // the same source for the queries from q0 on
+  ExactSource from_query(int64_t q0) const {
+    ExactSource s = *this;
+    s.Q += q0 * d;
+    if (s.qnorm != nullptr) s.qnorm += q0;
+    return s;
+  }
+};
+
 // out [nq][d] = shift + q / scale: the quint8 L2 scan's query (scan_begin's expression)
 int launch_qu8_query(const float* Q, int64_t nq, int d, Quant z, float* out, hipStream_t stream);
-// mode 0: max(|q|, 1e-12) (cosine); mode 1: sum q^2 (L2 expansion)
-int launch_qnorm(const float* Q, int64_t nq, int d, float* out, hipStream_t stream,
-                 int mode = 0);
+// out [nq] = max(|q|, 1e-12) (cosine)
+int launch_qnorm(const float* Q, int64_t nq, int d, float* out, hipStream_t stream);
 // Replace each candidate's key by its exact distance (the single-query scan's
 // summation order: bit-identical).  thr (optional): candidates whose key is
 // above the query's thr key are dropped (kEmpty) without being read.
-// qnorm: cosine only, max(|q|, 1e-12) as the scan computes it.
-// FX_DTYPE_QU8 (here and in the two launchers below; d % 16 == 0): z holds the
-// corpus's scale and zero point, and Q is what the quint8 scan keeps in LDS,
-// launch_qu8_query's q' for L2, the queries themselves otherwise.
-int launch_rescore(const void* X, int dtype, int64_t n, int d, int64_t row_base,
-                   const float* Q, const float* qnorm, int64_t nq, const uint32_t* count,
-                   uint64_t* cand, int cap, int metric, const uint64_t* thr, hipStream_t stream,
-                   Quant z = Quant());
+int launch_rescore(const ExactSource& src, int64_t nq, const uint32_t* count, uint64_t* cand,
+                   int cap, const uint64_t* thr, hipStream_t stream);
 // thr[q] = min(thr[q], the largest exact composite of the query's k rows
-// [nq][k] (global, -1 = missing: the query keeps its threshold)); scratch
-// [nq][2] uint64 zeroed before the first call (left zeroed by each call)
-int launch_exact_kth(const void* X, int dtype, int64_t n, int d, int64_t row_base,
-                     const float* Q, const float* qnorm, int64_t nq, int k, int64_t* rows,
-                     int metric, uint64_t* thr, hipStream_t stream, Quant z = Quant());
+// [nq][k] (global, -1 = missing: the query keeps its threshold)); rows is
+// overwritten
+int launch_exact_kth(const ExactSource& src, int64_t nq, int k, int64_t* rows, uint64_t* thr,
+                     hipStream_t stream);
 
-// run_merge (top-k by key of each query's first count[q] entries of keys
-// [nq][cap]) + launch_exact_kth in one launch, any cap (knn_batch.hip
-// select_kernel, streaming over LDS-sized chunks)
-// prune, prune_lists (these three): a plan that prunes (k ~ 1 000 over a
-// large buffer) first keeps the k smallest of every LDS-sized slice in
-// parallel (select_kernel MODE 3).  The plan fixes the slice count once
-// (BatchLayout::prune_lists = select_prune_lists(k, cap), 0 = no prune pass)
-// and reserves select_prune_bytes(nq, k, prune_lists) of scratch for it; the
-// launchers take both as given and read no option.
+// The selects (knn_select.hip, where each kernel is described): one workgroup
+// per query over its first count[q] entries of keys [nq][cap], any cap.
+//
+// A plan that prunes first keeps the k smallest of every LDS-sized slice in
+// parallel (prune_kernel).  The plan fixes the slice count once
+// (BatchLayout::prune_lists = select_prune_lists(k, cap), 0 = none) and
+// reserves select_prune_bytes of scratch; the launchers take both, together.
+struct PruneScratch {
+  uint64_t* lists = nullptr;  // [nq][count][k]
+  int count = 0;              // k-lists per query
+  bool on() const { return lists != nullptr && count > 0; }
+  uint64_t* from_query(int64_t q0, int k) const {
+    return on() ? lists + q0 * (int64_t)count * k : nullptr;
+  }
+};
 int select_prune_lists(int64_t k, int64_t cap);
 size_t select_prune_bytes(int64_t nq, int64_t k, int prune_lists);
-int launch_exact_threshold(const void* X, int dtype, int64_t n, int d, int64_t row_base,
-                           const float* Q, const float* qnorm, int64_t nq, const uint64_t* keys,
-                           int64_t cap, uint32_t* count, bool zero_count, int k, int metric,
-                           uint64_t* thr, hipStream_t stream, uint64_t* prune, int prune_lists,
-                           int64_t* topr, const uint64_t* gate_cand = nullptr,
-                           int64_t gate_num = 0, int64_t gate_den = 1, Quant z = Quant());
-// (gate_cand: launch_overflow_gate(gate_cand, count, thr, nq, cap, gate_num,
-// gate_den) follows on the new thresholds, fused into the select's workgroups
-// when the select computes them itself)
+// launch_overflow_gate(cand, count, thr, nq, cap, num, den) to follow a new
+// threshold; cand null: no gate
+struct OverflowGate {
+  const uint64_t* cand = nullptr;
+  int64_t num = 0, den = 1;
+};
+// thr[q] = min(thr[q], the largest exact composite of the k smallest keys'
+// rows): exact_threshold_kernel, or (a pruning plan with topr [nq][k]) the
+// select writes the rows and launch_exact_kth rescores them; then the gate.
+int launch_exact_threshold(const ExactSource& src, int64_t nq, const uint64_t* keys, int64_t cap,
+                           uint32_t* count, bool zero_count, int k, uint64_t* thr,
+                           PruneScratch prune, int64_t* topr, OverflowGate gate,
+                           hipStream_t stream);
 // thr[q] = min(thr[q], the k-th smallest of the query's first count[q] keys)
-// when it has at least k (run_merge's threshold-only level, any cap)
+// when it has at least k
 int launch_sample_threshold(const uint64_t* keys, int64_t nq, int64_t cap, uint32_t* count,
-                            bool zero_count, int k, uint64_t* thr, hipStream_t stream,
-                            uint64_t* prune, int prune_lists);
-// the final top-k of each query's first count[q] exact composites of keys
-// [nq][cap], sorted and decoded (run_merge's last level, one workgroup per
-// query, any cap); a query whose count exceeds alt_gate selects from its
-// alt_m entries of alt ([nq][alt_m], the overflow fallback scan's lists)
+                            bool zero_count, int k, uint64_t* thr, PruneScratch prune,
+                            hipStream_t stream);
+// the final top-k of each query's exact composites, sorted and decoded; a
+// query whose count exceeds alt_gate: of its alt_m entries of alt [nq][alt_m]
 int launch_final_select(const uint64_t* keys, int64_t nq, int64_t cap, const uint32_t* count,
                         int k, float* out_dist, int64_t* out_row, const uint64_t* alt,
-                        int64_t alt_m, int64_t alt_gate, hipStream_t stream, uint64_t* prune,
-                        int prune_lists);
+                        int64_t alt_m, int64_t alt_gate, PruneScratch prune, hipStream_t stream);
 
 // Batched filter on the fp16 matrix cores (knn_filter.hip: the entry points
 // and the fp16 error bound; the kernels: filter/*.inc, compiled into the
@@ -300,7 +316,8 @@ __device__ __forceinline__ uint32_t perm_row(uint64_t a, int64_t n, int64_t i) {
 // the last sample (count, cand: lb composites) that pass the new threshold thr,
 // scaled by num / den (the remaining tiles over the sample's), plus count: a
 // query predicted to exceed cap gets count = cap + 1 (the final pass skips it
-// and the exact scan recomputes it, fx_knn_reduce's gated fallback)
+// and the exact scan recomputes it, fx_knn_reduce's gated fallback).
+// knn_select.hip, beside the exact-threshold select that fuses it.
 int launch_overflow_gate(const uint64_t* cand, uint32_t* count, const uint64_t* thr, int64_t nq,
                          int cap, int64_t num, int64_t den, hipStream_t stream);
 // (thr, count: when given, each query's threshold is set empty and its append
@@ -319,7 +336,6 @@ int filter_tile_rows(int dtype);
 int launch_image(const float* X, int64_t n, int d, void* img, float* rowinfo, hipStream_t stream);
 int filter_query_pad(int64_t nq);
 int filter_dq(int d);
-int batch_tile_rows();
 int launch_encode(const float* dist, const int64_t* row, int64_t count, uint64_t* out,
                   hipStream_t stream);
 int launch_fill(void* x, int dtype, int64_t n, int64_t d, uint64_t seed, int64_t row_base,

@@ -23,7 +23,6 @@ int validate_quant(const fx_corpus& c);
 struct BatchLayout {
   int64_t cap = 0, tiles = 0, nq_pad = 0;
   int nphases = 0;
-  bool filter = false;  // fp16-MFMA filter + exact rescoring (knn_filter.hip)
   bool img8 = false;    // planned for an int8 filter image (filter_phases_i8)
   int dq = 0;
   int prune_lists = 0;  // img8: k-lists of the selects' prune pass (select_prune_lists), 0 = none
@@ -31,6 +30,37 @@ struct BatchLayout {
   MergePlan merge;
   size_t off_qnorm, off_thr, off_count, off_cand, off_merge, off_cand_ub, off_qh, off_qinfo,
       off_topr, off_qt, off_prune, total;
+};
+
+// The batched workspace as typed pointers: what a layout's offsets mean,
+// carved once for the phase drivers, the reduce and the test read-backs.
+struct BatchWorkspace {
+  float* qnorm;         // [nq] cosine: max(|q|, 1e-12)
+  uint64_t* thr;        // [nq] thresholds
+  uint32_t* count;      // [nq * kCountStride] appends per query
+  uint64_t* cand;       // [nq][cap] candidates (lower bounds, then exact composites)
+  char* merge;          // run_merge's scratch (fp16 filter plans)
+  uint64_t* cand_ub;    // [nq][cap] upper bounds of the final passes
+  void* qh;             // the filter's query tiles (fp16 or int8)
+  float* qinfo;         // the filter's per-query terms
+  int64_t* topr;        // [nq][k] rows of the k best upper bounds
+  float* qt;            // quint8 L2: the scan's transformed queries
+  PruneScratch prune;   // the selects' prune pass (none: off)
+  BatchWorkspace(const BatchLayout& b, void* ws) {
+    char* w = reinterpret_cast<char*>(ws);
+    qnorm = reinterpret_cast<float*>(w + b.off_qnorm);
+    thr = reinterpret_cast<uint64_t*>(w + b.off_thr);
+    count = reinterpret_cast<uint32_t*>(w + b.off_count);
+    cand = reinterpret_cast<uint64_t*>(w + b.off_cand);
+    merge = w + b.off_merge;
+    cand_ub = reinterpret_cast<uint64_t*>(w + b.off_cand_ub);
+    qh = w + b.off_qh;
+    qinfo = reinterpret_cast<float*>(w + b.off_qinfo);
+    topr = reinterpret_cast<int64_t*>(w + b.off_topr);
+    qt = reinterpret_cast<float*>(w + b.off_qt);
+    if (b.prune_lists > 0)
+      prune = PruneScratch{reinterpret_cast<uint64_t*>(w + b.off_prune), b.prune_lists};
+  }
 };
 
 struct SearchLayout {

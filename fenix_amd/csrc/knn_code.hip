@@ -9,8 +9,9 @@
 // code is among the `probes` composites nearest to the target (index.py:113-126).
 //
 //   assign_kernel    nearest codeword per (row, codebook).  An fp32 MFMA GEMM of
-//                    128-row x 256-codeword tiles (the batched search's tiling,
-//                    knn_batch.hip; f16 rows are widened while staging to LDS)
+//                    128-row x 256-codeword tiles (the tiling of the removed
+//                    fp32-MFMA batch kernel, DESIGN.md "Batched queries"; f16
+//                    rows are widened while staging to LDS)
 //                    whose epilogue turns each dot product into the metric's
 //                    distance, min-reduces 64-bit (order_key(dist) << 32 | index)
 //                    keys over each codebook segment in registers and lane

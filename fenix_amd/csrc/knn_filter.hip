@@ -9,7 +9,7 @@
 // rigorous bound e on |fp16 estimate - the single-query scan's f32 distance|
 // every (row, query) gets an interval [lb, ub] that contains the distance the
 // scan computes.  Rows are kept when lb can reach the query's threshold, and
-// every kept candidate is rescored exactly (knn_batch.hip rescore_kernel: the
+// every kept candidate is rescored exactly (knn_exact.hip rescore_kernel: the
 // scan's own summation order) before a result is taken.  No precision is given
 // up: the returned distances and rows are bit-identical to the f32 scan.
 //
@@ -580,53 +580,6 @@ uint64_t image8_perm(int64_t n) {
   uint64_t a = (uint64_t)((double)n * 0.6180339887498949) | 1u;
   while (gcd64(a, (uint64_t)n) != 1) a += 2;
   return a % (uint64_t)n;
-}
-
-// One workgroup per query (launch_overflow_gate, fx_internal.h), 8 loads in
-// flight per thread (k = 1 000: ~50 K F1 candidates per query, 63 -> ~10 us)
-constexpr int kGateThreads = 1024;
-__global__ void __launch_bounds__(kGateThreads) overflow_gate_kernel(
-    const uint64_t* __restrict__ cand, uint32_t* __restrict__ count,
-    const uint64_t* __restrict__ thr, int cap, int64_t num, int64_t den) {
-  const int64_t q = blockIdx.x;
-  __shared__ uint32_t tot;
-  const uint32_t c = count[q * kCountStride];
-  if (c > (uint32_t)cap) return;  // (already overflowing: recomputed anyway)
-  if (threadIdx.x == 0) tot = 0u;
-  __syncthreads();
-  const uint32_t t = (uint32_t)(thr[q] >> 32);
-  const uint64_t* cq = cand + q * (int64_t)cap;
-  uint32_t mine = 0u;
-  for (uint32_t b = threadIdx.x; b < c; b += kGateThreads * 8) {
-    uint64_t e[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t i = b + j * kGateThreads;
-      e[j] = i < c ? cq[i] : kEmpty;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) mine += b + j * kGateThreads < c && (uint32_t)(e[j] >> 32) <= t;
-  }
-  for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
-  if ((threadIdx.x & 63) == 0) atomicAdd(&tot, mine);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint64_t predicted = (uint64_t)c + ((uint64_t)tot * (uint64_t)num + (uint64_t)den - 1) /
-                                                 (uint64_t)den;
-    if (predicted > (uint64_t)cap) count[q * kCountStride] = (uint32_t)cap + 1u;
-  }
-}
-
-int launch_overflow_gate(const uint64_t* cand, uint32_t* count, const uint64_t* thr, int64_t nq,
-                         int cap, int64_t num, int64_t den, hipStream_t stream) {
-  if (nq <= 0) return FX_OK;
-  if (nq > 0x7fffffffll || den <= 0) {
-    set_error("overflow gate: nq=%lld den=%lld", (long long)nq, (long long)den);
-    return FX_EINVAL;
-  }
-  hipLaunchKernelGGL(overflow_gate_kernel, dim3((unsigned)nq), dim3(kGateThreads), 0, stream, cand,
-                     count, thr, cap, num, den);
-  return check_launch("overflow_gate_kernel");
 }
 
 int launch_image8(const void* X, int dtype, int64_t n, int d, void* img, float* rowinfo,

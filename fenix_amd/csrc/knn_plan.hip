@@ -39,22 +39,26 @@ int validate_quant(const fx_corpus& c) {
 
 // ---------------------------------------------------------------- batched --
 //
-// Batched queries (nq >= kBatchMinQ, f32) run the MFMA kernel of knn_batch.hip
-// in phases over growing row samples (L2: the GEMM gives |x|^2+|q|^2-2x.q,
-// rows pass on a rigorous fp32 lower bound and every appended candidate is
-// rescored exactly before any threshold or result is taken):
+// Batched queries (use_batched) run the MFMA filter (knn_filter.hip, kernels
+// in filter/*.inc) in phases over growing row samples.  The filter brackets
+// every (row, query) distance between a rigorous lower and upper bound and
+// appends the pairs whose lower bound reaches the query's threshold to the
+// query's candidate buffer of `cap` slots:
 //   phase 0: a sample of <= cap rows, no threshold -> every (row, query) kept;
-//   phase i: a sample ~cap/(4k) times larger, threshold = the k-th composite
-//            of phase i-1 (an upper bound of the global k-th: the k-th of any
-//            row subset is), so it keeps ~cap/4 candidates per query;
-//   last:    every row with the last threshold -> final select.
+//   phase i: a sample ~cap/(4k) times larger (plan_phases; an int8 image:
+//            plan_phases_i8's prefixes), threshold = the k-th upper bound of
+//            phase i-1 (an upper bound of the global k-th distance: the k-th
+//            of any row subset is), so it keeps ~cap/4 candidates per query;
+//   last:    every row against the last threshold.
+// The kept candidates are rescored exactly, in the single-query scan's own
+// arithmetic (knn_exact.hip), before any result is taken from them, and the
+// top k of the exact keys is the answer (run_merge; an int8 image: the
+// selects of knn_select.hip, which also tighten the thresholds with exact
+// distances between the phases).  The drivers are filter_phases and
+// filter_phases_i8 (capi.hip).
 // A query whose final candidates overflow `cap` is recomputed exactly by the
 // single-query scan, gated on the device (fx_knn_reduce: no host sync).
 static constexpr int64_t kListLen = 4096;  // candidate buffer viewed as lists
-
-// The fp16-MFMA filter (knn_filter.hip, kernels in filter/*.inc).  Diagnostic builds keep the
-// rejected fp32-MFMA batch kernel (knn_batch.hip) behind FX_BATCH_FILTER=0.
-static bool use_filter() { return diag_env("FX_BATCH_FILTER", 1) != 0; }
 
 // A single query over an f32 corpus of at least this many bytes takes the
 // batched path when an int8 filter image is supplied (the *_img8 entry
@@ -64,7 +68,7 @@ static constexpr int64_t kSingleImageMinBytes = (int64_t)4 << 30;
 // Int8 images serve k <= option "i8_max_k" (1 024 = kMaxK, every k the
 // filter plans).  Round 3's 64 K slots overflowed at k = 1 000 (6.25M x 1536
 // fp16 IP, profiles/r03_f16_int8_image.log); with the 4x buffer (256 K slots
-// at k = 1 000), the pruned selects (select_kernel MODE 3) and the shared LDS
+// at k = 1 000), the pruned selects (prune_kernel) and the shared LDS
 // append segments, 60 single queries (normal, near, clustered corpus) kept
 // 94-122 K candidates, none overflowed, 1.67 vs 2.84 ms for the exact scan,
 // bit-identical (profiles/r06_k1000_sweep*.json); batches at k 300-1 000 are
@@ -86,8 +90,7 @@ static int64_t i8_max_k() { return option(kOptI8MaxK); }
 // 2 / 16 / 64 / 256 queries against 2.4 / 18.4 / 72.5 / 289 ms).
 static bool use_batched_qu8(int64_t nq, int64_t d, bool aligned, int64_t n, bool img8, int64_t k) {
   const int64_t min_q = option(kOptBatchMinQ) >= 2 ? option(kOptBatchMinQ) : 2;
-  if (!img8 || !use_filter() || nq < min_q || !aligned || d % 16 != 0 || k > i8_max_k())
-    return false;
+  if (!img8 || nq < min_q || !aligned || d % 16 != 0 || k > i8_max_k()) return false;
   return (double)nq * (double)n * (double)d >= (double)option(kOptQu8BatchMinWork);
 }
 
@@ -101,12 +104,11 @@ static bool use_batched(int64_t nq, int dtype, int64_t d, bool aligned, int64_t 
   if (nq == 1 && img8 && k <= i8_max_k() && option(kOptSingleImage) != 0 && d % 8 == 0 &&
       n * d * (dtype == FX_DTYPE_F32 ? 4 : 2) >= kSingleImageMinBytes)
     min_q = 1;
-  if (!use_filter()) min_q = 8;  // the fp32-MFMA kernel breaks even with scans at ~8 queries
   if (nq < min_q || !aligned) return false;
   // the rescoring repeats the scan's 16-B slot order: f32 rows need d % 4 == 0,
-  // f16 rows d % 8 == 0 (and the fp16 filter: the fp32-MFMA kernel reads f32 only)
+  // f16 rows d % 8 == 0
   if (dtype == FX_DTYPE_F32) return d % 4 == 0;
-  return dtype == FX_DTYPE_F16 && d % 8 == 0 && use_filter();
+  return dtype == FX_DTYPE_F16 && d % 8 == 0;
 }
 
 // Nested row samples of the batched phases: phase i scans every stride_i-th
@@ -167,14 +169,13 @@ static int plan_phases_i8(BatchLayout* b, int64_t tr, int64_t r1, int64_t r2) {
 
 static int plan_batched(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, bool img8,
                         BatchLayout* b) {
-  b->filter = use_filter();
-  b->img8 = img8 && b->filter;
-  const int64_t tr = b->filter ? filter_tile_rows(dtype) : batch_tile_rows();
+  b->img8 = img8;
+  const int64_t tr = filter_tile_rows(dtype);
   b->cap = 64 * k > 16384 ? 64 * k : 16384;
   // int8 images: 4x the buffer.  Their bounds keep whole clusters of a
   // clustered corpus against a generic query (10M x 768, x + 10 x0 per
   // 1 000 rows, 256 cosine queries: median 10 K, largest 33 K candidates);
-  // every consumer reads only the count it was given (select_kernel streams
+  // every consumer reads only the count it was given (the selects stream
   // any count), so the larger buffer costs memory, not time
   if (b->img8) b->cap *= 4;
   if (option(kOptBatchCap) >= 16 * k) b->cap = option(kOptBatchCap);  // test: small buffers
@@ -213,21 +214,19 @@ static int plan_batched(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, 
   off += align256((size_t)nq * b->cap * 8);
   b->off_merge = off;
   off += align256(b->merge.ws_bytes);
-  if (b->filter) {
-    b->dq = filter_dq((int)d);
-    b->nq_pad = (nq + filter_query_pad(nq) - 1) / filter_query_pad(nq) * filter_query_pad(nq);
-    b->off_cand_ub = off;
-    off += align256((size_t)nq * b->cap * 8);
-    // fp16 query tiles, or int8 ones padded to 256 queries (int8 filter images)
-    const size_t q16 = (size_t)b->nq_pad * b->dq * 2, q8 = (size_t)((nq + 255) / 256 * 256) * b->dq;
-    b->off_qh = off;
-    off += align256(q16 > q8 ? q16 : q8);
-    b->off_qinfo = off;
-    off += align256((size_t)nq * 16);
-    // the rows of the k best candidates by upper bound (int8 images: exact thresholds)
-    b->off_topr = off;
-    off += align256((size_t)nq * k * 8);
-  }
+  b->dq = filter_dq((int)d);
+  b->nq_pad = (nq + filter_query_pad(nq) - 1) / filter_query_pad(nq) * filter_query_pad(nq);
+  b->off_cand_ub = off;
+  off += align256((size_t)nq * b->cap * 8);
+  // fp16 query tiles, or int8 ones padded to 256 queries (int8 filter images)
+  const size_t q16 = (size_t)b->nq_pad * b->dq * 2, q8 = (size_t)((nq + 255) / 256 * 256) * b->dq;
+  b->off_qh = off;
+  off += align256(q16 > q8 ? q16 : q8);
+  b->off_qinfo = off;
+  off += align256((size_t)nq * 16);
+  // the rows of the k best candidates by upper bound (int8 images: exact thresholds)
+  b->off_topr = off;
+  off += align256((size_t)nq * k * 8);
   // quint8: the L2 scan's transformed queries (launch_qu8_query)
   b->off_qt = off;
   if (dtype == FX_DTYPE_QU8) off += align256((size_t)nq * d * 4);

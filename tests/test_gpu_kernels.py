@@ -1259,7 +1259,7 @@ def test_search_shards_one_merge_equals_per_shard(eng, metric, dtype):
 def test_int8_large_k_pruned_selects_bit_identical(eng, metric, dtype, n, d, nq, k):
     """k >= 512 through the int8 image (option i8_max_k raised): every
     select over the large candidate buffer first keeps the k smallest of each
-    16 K slice in parallel (select_kernel MODE 3, knn_batch.hip) and then
+    16 K slice in parallel (prune_kernel, knn_select.hip) and then
     selects from those k-lists.  Results equal the exact scan bit for bit,
     and through the overflow fallback (force_fallback: the final select
     takes the fallback lists, never the pruned ones).  Reference: the

@@ -2,7 +2,7 @@
 (fx_knn_search_img8_ex): the int8-MFMA filter runs over an image of the
 dequantised rows (csrc/knn_filter.hip image8_qu8_kernel) and the candidates
 are rescored from the codes in the quint8 scan's own arithmetic
-(csrc/knn_batch.hip exact_distance16_qu8).
+(csrc/fx_exact.h exact_distance16_qu8).
 
 * bits: rows and distance bits equal per-query exact scans (option "batched"
   0) on every kernel a batch size reaches, for every metric;
