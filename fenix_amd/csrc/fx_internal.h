@@ -108,19 +108,20 @@ struct ScanArgs {
 typedef void (*ScanKernelFn)(ScanArgs);
 
 struct ScanPlan {
-  ScanKernelFn fn;
+  ScanKernelFn fn;  // register tiles: serves every scan
   int W, L, U, cap;
   size_t qbytes, smem;
   int64_t blocks, rows_per_block, nlists;
-  int interleave;  // ScanArgs::interleave for the register-tile kernels
-  // quint8 rows staged by LDS-DMA (plain contiguous scans: no mask, no row
-  // list); null when not applicable.  Same rows_per_block (its U divides it).
-  ScanKernelFn fn_dma;
-  size_t smem_dma;
-  // f32 / f16 rows of exactly 16 L slots streamed through a register ring
-  // (plain scans: no mask, no row list); null when not applicable or switched
-  // off.  Same LDS, grid and rows_per_block as fn.
-  ScanKernelFn fn_stream;
+  int interleave;  // ScanArgs::interleave
+  // Plain scans (no mask, no row list) where a ring kernel applies and is not
+  // switched off, else null: f32 / f16 rows of exactly 16 L slots streamed
+  // through a register ring (smem_plain == smem), quint8 rows staged by
+  // LDS-DMA (smem_plain: smem plus the ring).  Same grid and rows_per_block
+  // as fn (the DMA ring's U divides it).  plain_name: the kernel for
+  // check_launch.
+  ScanKernelFn fn_plain;
+  size_t smem_plain;
+  const char* plain_name;
 };
 
 int plan_scan(int64_t n, int64_t d, int dtype, int64_t k, int metric, bool aligned, ScanPlan* p);

@@ -1,7 +1,7 @@
 // Exact distances for the batched filter's candidates: the query norm and the
 // quint8 query transform the scan's formulas need, the rescoring of a
 // candidate buffer in place, and the exact k-th of a query's k best rows.
-// Every distance is row_distance16 (fx_exact.h), the scan's value bit for bit.
+// Every distance is row_distance16 (fx_exact.h), the scan's own arithmetic.
 #include "fx_exact.h"
 
 namespace fx {

@@ -433,9 +433,8 @@ __global__ void __launch_bounds__(256) image8_kernel(const T* __restrict__ X, in
 
 // The same image and row terms for quint8 codes (FX_DTYPE_QU8): the rows are
 // x = sigma y with y = code - zero point, integers in [-255, 255], and the
-// quint8 scan (knn_scan.hip tile_accumulate's sizeof(T) == 1 branch,
-// tile_finish) never forms x: it sums in code units and multiplies by sigma
-// at the end.  Everything below is derived from the integers.
+// quint8 scan (fx_exact.h slot_accumulate_qu8, sums_distance) never forms x:
+// it sums in code units and multiplies by sigma at the end.  Everything below is derived from the integers.
 //
 // Row terms.  Y2 = sum y^2 is an exact integer.  The row is quantised in code
 // units, t = max(max|y| / 127, sqrt(Y2) / i8_norm_cap(d)), x~ = rint(y / t)

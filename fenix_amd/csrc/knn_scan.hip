@@ -22,7 +22,9 @@
 // those lists to the final sorted top-k.  No barriers in the main loop.
 #include <stdlib.h>
 
-#include "fx_internal.h"
+#include <type_traits>
+
+#include "fx_exact.h"
 #include "fx_select.h"
 
 // Rows in flight per 16-lane group (U) for each slot count L (slots of 16 B
@@ -100,15 +102,6 @@ template <typename T>
 struct VecT<T, 1> {
   typedef T type;
 };
-
-template <int W, typename V>
-__device__ __forceinline__ float elem(const V& v, int e) {
-  if constexpr (W == 1) {
-    return (float)v;
-  } else {
-    return (float)v[e];
-  }
-}
 
 template <typename V>
 __device__ __forceinline__ V load_stream(const V* p) {
@@ -245,12 +238,19 @@ __device__ int wave_compact(uint64_t* buf, int cnt, uint64_t T, int quota_eq, in
 // the first sum: the waves of a CU cover each other's bubbles, a wave does not
 // overlap its own.  stream_scan_kernel below is the form that does.
 
-template <typename T, int W, int L, int U>
-struct RowTile {
-  typename VecT<T, W>::type v[U][L];
+// The U rows of one lane group's tile ...
+template <int U>
+struct TileRows {
   int64_t row[U];  // position in the scanned range (list index with a row list)
   int64_t src[U];  // corpus row (== row without a row list)
   bool valid[U];
+};
+// ... and, for the register tiles, their data (first: with the rows first the
+// U = 8 and U = 2 tile kernels spill more SGPRs)
+template <typename T, int W, int L, int U>
+struct RowTile {
+  typename VecT<T, W>::type v[U][L];
+  TileRows<U> rows;
 };
 
 struct ScanCtx {
@@ -265,9 +265,20 @@ struct ScanCtx {
   bool topk;
 };
 
+// row u of the lane group's tile at row `it` of a plain scan (the rings;
+// tile_load adds the row list and the mask, and through this helper it
+// compiles to more SGPR spills)
+template <int U>
+__device__ __forceinline__ void tile_row(TileRows<U>& t, int u, int64_t it, const ScanCtx& c) {
+  t.row[u] = it + u * 4 + c.grp;
+  t.valid[u] = t.row[u] < c.hi;
+  t.src[u] = t.row[u];
+}
+
 template <typename T, int W, int L, int U>
-__device__ __forceinline__ void tile_load(RowTile<T, W, L, U>& t, int64_t it, int ch,
+__device__ __forceinline__ void tile_load(RowTile<T, W, L, U>& tile, int64_t it, int ch,
                                           const ScanCtx& c) {
+  TileRows<U>& t = tile.rows;
   using V = typename VecT<T, W>::type;
   const ScanArgs& a = *c.a;
   const T* X = reinterpret_cast<const T*>(a.X);
@@ -287,32 +298,12 @@ __device__ __forceinline__ void tile_load(RowTile<T, W, L, U>& t, int64_t it, in
     for (int cc = 0; cc < L; ++cc) {
       const int s = ch * 16 * L + cc * 16 + c.jl;
       if (t.valid[u] && s < c.S) {
-        t.v[u][cc] = load_stream(rp + s);
+        tile.v[u][cc] = load_stream(rp + s);
       } else if constexpr (sizeof(T) == 1) {
-        t.v[u][cc] = V((T)c.qshift);  // the zero-point code dequantises to exactly 0
+        tile.v[u][cc] = V((T)c.qshift);  // the zero-point code dequantises to exactly 0
       } else {
-        t.v[u][cc] = V(0);
+        tile.v[u][cc] = V(0);
       }
-    }
-  }
-}
-
-// One 16-B slot of one f32 / f16 row against the matching query elements, in
-// ascending element order (every path sums a row in the same order).
-template <int W, int METRIC, typename V>
-__device__ __forceinline__ void slot_accumulate(const V& v, const float (&qv)[W], float& acc,
-                                                float& acc2) {
-#pragma unroll
-  for (int e = 0; e < W; ++e) {
-    const float x = elem<W>(v, e);
-    if constexpr (METRIC == 0) {
-      const float d = x - qv[e];
-      acc = fmaf(d, d, acc);
-    } else if constexpr (METRIC == 1) {
-      acc = fmaf(x, qv[e], acc);
-    } else {
-      acc = fmaf(x, qv[e], acc);
-      acc2 = fmaf(x, x, acc2);
     }
   }
 }
@@ -322,16 +313,8 @@ __device__ __forceinline__ void tile_accumulate(const RowTile<T, W, L, U>& t, in
                                                 const ScanCtx& c, float (&acc)[U],
                                                 float (&acc2)[U]) {
   if constexpr (sizeof(T) == 1) {
-    // quint8 codes, value = qscale * (code - qshift).  Per element: one
-    // ubyte->f32 convert and packed fp32 ops on pairs (v_pk_add/v_pk_fma):
-    //   L2   d = code - q'  with q' = qshift + q/qscale (query pre-transformed
-    //        in LDS), sum d^2;  distance = qscale * sqrt(sum)
-    //   IP   sum (code - qshift) q;            distance = -qscale * sum
-    //   cos  sum (code - qshift) q and (code - qshift)^2, scaled in tile_finish
-    // (vs dequantise-then-compute: 2-2.5 VALU ops per byte instead of 5-6; the
-    // scan was VALU-bound at 3.6 TB/s).
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef float f16v __attribute__((ext_vector_type(16)));
+    // quint8 codes in code units (slot_accumulate_qu8), the query (q' for L2:
+    // scan_begin) read from LDS
     static_assert(W == 16 || W == 1, "quint8 rows are scanned 16 codes per lane");
     const f2 z2 = {c.qshift, c.qshift};
 #pragma unroll
@@ -357,24 +340,9 @@ __device__ __forceinline__ void tile_accumulate(const RowTile<T, W, L, U>& t, in
 #pragma unroll
         for (int p = 0; p < 8; ++p) q2[p] = qp[p];
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const f16v xf = __builtin_convertvector(t.v[u][cc], f16v);
-          f2 a2 = {0.f, 0.f}, b2 = {0.f, 0.f};
-#pragma unroll
-          for (int p = 0; p < 8; ++p) {
-            const f2 x2 = {xf[2 * p], xf[2 * p + 1]};
-            if constexpr (METRIC == 0) {
-              const f2 d = x2 - q2[p];
-              a2 = __builtin_elementwise_fma(d, d, a2);
-            } else {
-              const f2 d = x2 - z2;
-              a2 = __builtin_elementwise_fma(d, q2[p], a2);
-              if constexpr (METRIC == 2) b2 = __builtin_elementwise_fma(d, d, b2);
-            }
-          }
-          acc[u] += a2.x + a2.y;
-          if constexpr (METRIC == 2) acc2[u] += b2.x + b2.y;
-        }
+        for (int u = 0; u < U; ++u)
+          slot_accumulate_qu8<METRIC>(t.v[u][cc], [&](int p) { return q2[p]; }, z2, acc[u],
+                                      acc2[u]);
       }
     }
     return;
@@ -391,35 +359,14 @@ __device__ __forceinline__ void tile_accumulate(const RowTile<T, W, L, U>& t, in
 }
 
 // Distances of the tile's rows -> output (distance mode) or candidate list.
-template <typename T, int W, int L, int U, int METRIC>
-__device__ __forceinline__ void tile_finish(const RowTile<T, W, L, U>& t, float (&acc)[U],
+template <bool QU8, int U, int METRIC>
+__device__ __forceinline__ void tile_finish(const TileRows<U>& t, float (&acc)[U],
                                             float (&acc2)[U], const ScanCtx& c, uint64_t& thr,
                                             int& cnt) {
   const ScanArgs& a = *c.a;
   float dist[U];
 #pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const float s1 = sum16(acc[u]);
-    if constexpr (sizeof(T) == 1) {  // quint8: sums are in code units
-      if constexpr (METRIC == 0) {
-        dist[u] = c.qscale * sqrtf(s1);
-      } else if constexpr (METRIC == 1) {
-        dist[u] = -(c.qscale * s1);
-      } else {
-        const float s2 = sum16(acc2[u]);
-        const float nx = fmaxf(c.qscale * sqrtf(s2), 1e-12f);
-        dist[u] = 0.5f - 0.5f * ((c.qscale * s1) / (nx * c.qnorm));
-      }
-    } else if constexpr (METRIC == 0) {
-      dist[u] = sqrtf(s1);
-    } else if constexpr (METRIC == 1) {
-      dist[u] = -s1;
-    } else {
-      const float s2 = sum16(acc2[u]);
-      const float nx = fmaxf(sqrtf(s2), 1e-12f);
-      dist[u] = 0.5f - 0.5f * (s1 / (nx * c.qnorm));
-    }
-  }
+  for (int u = 0; u < U; ++u) dist[u] = sums_distance<METRIC, QU8>(acc[u], acc2[u], c.qnorm, c.qscale);
   if (!c.topk) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -454,7 +401,7 @@ __device__ __forceinline__ void tile_consume(const RowTile<T, W, L, U>& t, const
 #pragma unroll
   for (int u = 0; u < U; ++u) acc[u] = acc2[u] = 0.f;
   tile_accumulate<T, W, L, U, METRIC>(t, 0, c, acc, acc2);
-  tile_finish<T, W, L, U, METRIC>(t, acc, acc2, c, thr, cnt);
+  tile_finish<sizeof(T) == 1, U, METRIC>(t.rows, acc, acc2, c, thr, cnt);
 }
 
 #ifndef FX_Q8_WAVES
@@ -598,13 +545,11 @@ __device__ __forceinline__ void ring_tile(typename VecT<T, W>::type (&ring)[R],
                                           const int64_t (&cur)[U], const int64_t (&nxt)[U],
                                           const float (&qreg)[QREG ? L : 1][W], int64_t it,
                                           const ScanCtx& c, uint64_t& thr, int& cnt) {
-  RowTile<T, W, 1, U> t;  // rows only: the data is in the ring
+  TileRows<U> t;
   float acc[U], acc2[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    t.row[u] = it + u * 4 + c.grp;
-    t.valid[u] = t.row[u] < c.hi;
-    t.src[u] = t.row[u];
+    tile_row(t, u, it, c);
     acc[u] = acc2[u] = 0.f;
   }
 #pragma unroll
@@ -629,7 +574,7 @@ __device__ __forceinline__ void ring_tile(typename VecT<T, W>::type (&ring)[R],
       }
     }
   }
-  tile_finish<T, W, 1, U, METRIC>(t, acc, acc2, c, thr, cnt);
+  tile_finish<false, U, METRIC>(t, acc, acc2, c, thr, cnt);
 }
 
 // Streaming kernel for plain scans (no mask, no row list) of f32 / f16 rows of
@@ -689,11 +634,109 @@ __global__ void __launch_bounds__(256, 2) stream_scan_kernel(ScanArgs a) {
   scan_end(a, smem, c, cnt);
 }
 
-template <typename T, int W, int L, int U, int METRIC, bool PIPE, bool DMA = false>
+// quint8 rows of one pass (d <= 256 L), plain scans (no mask, no row list;
+// plan_scan / launch_scan), through a per-wave LDS ring of FX_Q8DMA_STAGES
+// tiles after the block's LDS: rows in flight cost no registers.  One
+// global_load_lds per 16-B slot column (64 lanes x 16 B = the wave's 4U rows'
+// slot cc), issued FX_Q8DMA_STAGES - 1 tiles ahead; the counted vmcnt leaves
+// the later tiles in flight.  Slots past the row end read a valid dummy and
+// are replaced by the zero-point code in registers; rows past the range are
+// clamped to its last row (never consumed).
+template <int L, int U, int METRIC>
+__global__ void __launch_bounds__(256, kMinWaves<uint8_t>) dma_scan_kernel(ScanArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  typedef uint8_t V __attribute__((ext_vector_type(16)));
+
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int S = a.d / 16;
+  constexpr int CH = 16 * L;
+  const int nch = (S + CH - 1) / CH;
+  ScanCtx c;
+  if (!scan_begin<uint8_t, 16, METRIC>(a, smem, nch * CH * 16, c)) return;
+  int64_t lo, gstep;
+  scan_partition<U>(a, c, lo, gstep);
+
+  uint64_t thr = kEmpty;
+  int cnt = 0;
+  constexpr int R = FX_Q8DMA_STAGES;
+  constexpr int kTileBytes = U * L * 1024;
+  unsigned char* ring = smem + a.qbytes + (size_t)4 * a.cap * 8 + 4 * 256 * 4 +
+                        (size_t)__builtin_amdgcn_readfirstlane(wid) * R * kTileBytes;
+  const int64_t first = lo + (int64_t)wid * 4 * U;
+  const int64_t ntile = first < c.hi ? (c.hi - first + gstep - 1) / gstep : 0;
+  const f2 z2 = {c.qshift, c.qshift};
+  f2 qreg[L][8];  // this lane's query slots (jl, jl + 16, ...), held in registers
+#pragma unroll
+  for (int cc = 0; cc < L; ++cc) {
+    const f2* qp = reinterpret_cast<const f2*>(c.q_lds + (cc * 16 + c.jl) * 16);
+#pragma unroll
+    for (int p = 0; p < 8; ++p) qreg[cc][p] = qp[p];
+  }
+  // The wave's tile jj -> ring slot `slot`.  Expanded in place, in the prologue
+  // and in the loop: through a lambda or a function the steady state's address
+  // arithmetic is scheduled differently and the 10M x 768 scan measured 0.25 %
+  // slower (profiles/scan_arith_resources.txt).
+#define FX_DMA_ISSUE(jj, slot)                                                                  \
+  _Pragma("unroll") for (int u = 0; u < U; ++u) {                                               \
+    int64_t row = first + (jj) * gstep + u * 4 + c.grp;                                          \
+    if (row >= c.hi) row = c.hi - 1;                                                             \
+    _Pragma("unroll") for (int cc = 0; cc < L; ++cc) {                                          \
+      const int sl = cc * 16 + c.jl;                                                             \
+      const void* g =                                                                            \
+          reinterpret_cast<const uint8_t*>(a.X) + row * (int64_t)a.d + (sl < S ? sl : 0) * 16;   \
+      __builtin_amdgcn_global_load_lds(                                                          \
+          g,                                                                                     \
+          (__attribute__((address_space(3))) void*)(ring + (slot) * kTileBytes +                 \
+                                                    (u * L + cc) * 1024),                        \
+          16, 0, FX_Q8DMA_AUX);                                                                  \
+    }                                                                                            \
+  }
+  int slot_i = 0, slot_n = R - 1;
+#pragma unroll
+  for (int j = 0; j < R - 1; ++j) {
+    const int64_t jj = j;
+    FX_DMA_ISSUE(jj, j)
+  }
+  for (int64_t i = 0; i < ntile; ++i) {
+    {
+      const int64_t jj = i + R - 1;
+      FX_DMA_ISSUE(jj, slot_n)
+    }
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R - 1) * U * L) : "memory");
+    RowTile<uint8_t, 16, L, U> t;  // the ring's oldest tile -> registers
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      tile_row(t.rows, u, first + i * gstep, c);
+#pragma unroll
+      for (int cc = 0; cc < L; ++cc) {
+        t.v[u][cc] = *reinterpret_cast<const V*>(ring + slot_i * kTileBytes +
+                                                 (u * L + cc) * 1024 + lane * 16);
+        if (cc * 16 + c.jl >= S) t.v[u][cc] = V((uint8_t)c.qshift);  // dequantises to 0
+      }
+    }
+    float acc[U], acc2[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      acc[u] = acc2[u] = 0.f;
+#pragma unroll
+      for (int cc = 0; cc < L; ++cc)
+        slot_accumulate_qu8<METRIC>(t.v[u][cc], [&](int p) { return qreg[cc][p]; }, z2,
+                                    acc[u], acc2[u]);
+    }
+    tile_finish<true, U, METRIC>(t.rows, acc, acc2, c, thr, cnt);
+    slot_i = slot_i == R - 1 ? 0 : slot_i + 1;
+    slot_n = slot_n == R - 1 ? 0 : slot_n + 1;
+  }
+#undef FX_DMA_ISSUE
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the ring's tail loads
+  scan_end(a, smem, c, cnt);
+}
+
+template <typename T, int W, int L, int U, int METRIC, bool PIPE>
 __global__ void __launch_bounds__(256, kMinWaves<T>) scan_kernel(ScanArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wid = threadIdx.x >> 6;
   const int S = a.d / W;
   constexpr int CH = 16 * L;
   const int nch = (S + CH - 1) / CH;
@@ -706,113 +749,7 @@ __global__ void __launch_bounds__(256, kMinWaves<T>) scan_kernel(ScanArgs a) {
   int cnt = 0;
   RowTile<T, W, L, U> tA, tB;
 
-  if constexpr (DMA) {
-    // Per-wave ring of FX_Q8DMA_STAGES tiles after the block's LDS: one
-    // global_load_lds per 16-B slot column (64 lanes x 16 B = the wave's 4U
-    // rows' slot cc), issued FX_Q8DMA_STAGES - 1 tiles ahead; the counted
-    // vmcnt leaves the later tiles in flight.  Slots past the row end read a
-    // valid dummy and are replaced by the zero-point code in registers; rows
-    // past the range are clamped to its last row (never consumed).  One pass
-    // per row (nch == 1), no mask, no row list (plan_scan / launch_scan).
-    constexpr int R = FX_Q8DMA_STAGES;
-    constexpr int kTileBytes = U * L * 1024;
-    unsigned char* ring = smem + a.qbytes + (size_t)4 * a.cap * 8 + 4 * 256 * 4 +
-                          (size_t)__builtin_amdgcn_readfirstlane(wid) * R * kTileBytes;
-    const int64_t first = lo + (int64_t)wid * 4 * U;
-    const int64_t ntile = first < c.hi ? (c.hi - first + gstep - 1) / gstep : 0;
-    using V = typename VecT<T, W>::type;
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef float f16v __attribute__((ext_vector_type(16)));
-    static_assert(W == 16, "the DMA path scans 16 quint8 codes per lane slot");
-    const f2 z2 = {c.qshift, c.qshift};
-    f2 qreg[L][8];  // this lane's query slots (jl, jl + 16, ...), held in registers
-#pragma unroll
-    for (int cc = 0; cc < L; ++cc) {
-      const f2* qp = reinterpret_cast<const f2*>(c.q_lds + (cc * 16 + c.jl) * W);
-#pragma unroll
-      for (int p = 0; p < 8; ++p) qreg[cc][p] = qp[p];
-    }
-    int slot_i = 0, slot_n = R - 1;
-#pragma unroll
-    for (int j = 0; j < R - 1; ++j) {
-        const int64_t jj = j;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          int64_t row = first + jj * gstep + u * 4 + c.grp;
-          if (row >= c.hi) row = c.hi - 1;
-#pragma unroll
-          for (int cc = 0; cc < L; ++cc) {
-            const int sl = cc * 16 + c.jl;
-            const void* g = reinterpret_cast<const T*>(a.X) + row * (int64_t)a.d + (sl < S ? sl : 0) * 16;
-            __builtin_amdgcn_global_load_lds(
-                g, (__attribute__((address_space(3))) void*)(ring + j * kTileBytes + (u * L + cc) * 1024),
-                16, 0, FX_Q8DMA_AUX);
-          }
-        }
-      }
-    for (int64_t i = 0; i < ntile; ++i) {
-      {
-        const int64_t jj = i + R - 1;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          int64_t row = first + jj * gstep + u * 4 + c.grp;
-          if (row >= c.hi) row = c.hi - 1;
-#pragma unroll
-          for (int cc = 0; cc < L; ++cc) {
-            const int sl = cc * 16 + c.jl;
-            const void* g = reinterpret_cast<const T*>(a.X) + row * (int64_t)a.d + (sl < S ? sl : 0) * 16;
-            __builtin_amdgcn_global_load_lds(
-                g, (__attribute__((address_space(3))) void*)(ring + slot_n * kTileBytes + (u * L + cc) * 1024),
-                16, 0, FX_Q8DMA_AUX);
-          }
-        }
-      }
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R - 1) * U * L) : "memory");
-      RowTile<T, W, L, U> t;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        t.row[u] = first + i * gstep + u * 4 + c.grp;
-        t.valid[u] = t.row[u] < c.hi;
-        t.src[u] = t.row[u];
-#pragma unroll
-        for (int cc = 0; cc < L; ++cc) {
-          t.v[u][cc] = *reinterpret_cast<const V*>(ring + slot_i * kTileBytes +
-                                                   (u * L + cc) * 1024 + lane * 16);
-          if (cc * 16 + c.jl >= S) t.v[u][cc] = V((T)c.qshift);  // dequantises to 0
-        }
-      }
-      // tile_accumulate's quint8 arithmetic, operation for operation (so the
-      // distances equal the register-tile path's), with the query in registers
-      float acc[U], acc2[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        acc[u] = acc2[u] = 0.f;
-#pragma unroll
-        for (int cc = 0; cc < L; ++cc) {
-          const f16v xf = __builtin_convertvector(t.v[u][cc], f16v);
-          f2 a2 = {0.f, 0.f}, b2 = {0.f, 0.f};
-#pragma unroll
-          for (int p = 0; p < 8; ++p) {
-            const f2 x2 = {xf[2 * p], xf[2 * p + 1]};
-            if constexpr (METRIC == 0) {
-              const f2 dd = x2 - qreg[cc][p];
-              a2 = __builtin_elementwise_fma(dd, dd, a2);
-            } else {
-              const f2 dd = x2 - z2;
-              a2 = __builtin_elementwise_fma(dd, qreg[cc][p], a2);
-              if constexpr (METRIC == 2) b2 = __builtin_elementwise_fma(dd, dd, b2);
-            }
-          }
-          acc[u] += a2.x + a2.y;
-          if constexpr (METRIC == 2) acc2[u] += b2.x + b2.y;
-        }
-      }
-      tile_finish<T, W, L, U, METRIC>(t, acc, acc2, c, thr, cnt);
-      slot_i = slot_i == R - 1 ? 0 : slot_i + 1;
-      slot_n = slot_n == R - 1 ? 0 : slot_n + 1;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the ring's tail loads
-  } else if (PIPE && nch == 1 && !(a.interleave & 2)) {
+  if (PIPE && nch == 1 && !(a.interleave & 2)) {
     int64_t it = lo + (int64_t)wid * 4 * U;
     if (it < c.hi) tile_load(tA, it, 0, c);
     for (; it < c.hi; it += 2 * gstep) {
@@ -834,7 +771,7 @@ __global__ void __launch_bounds__(256, kMinWaves<T>) scan_kernel(ScanArgs a) {
         tile_load(tA, it, ch, c);
         tile_accumulate<T, W, L, U, METRIC>(tA, ch, c, acc, acc2);
       }
-      tile_finish<T, W, L, U, METRIC>(tA, acc, acc2, c, thr, cnt);
+      tile_finish<sizeof(T) == 1, U, METRIC>(tA.rows, acc, acc2, c, thr, cnt);
     }
   }
 
@@ -854,146 +791,68 @@ static constexpr int kInterleaveDefault = FX_SCAN_INTERLEAVE_DEFAULT;
 template <typename T, int L>
 constexpr bool kPipe = !(sizeof(T) == 2 && L >= 12);
 
-template <typename T, int W, int METRIC>
-static ScanKernelFn pick_l(int L) {
-  if constexpr (sizeof(T) == 1) {
-    switch (L) {
-      case 1: return scan_kernel<T, W, 1, FX_Q1, METRIC, true>;
-      case 2: return scan_kernel<T, W, 2, FX_Q2, METRIC, true>;
-      case 3: return scan_kernel<T, W, 3, FX_Q3, METRIC, true>;
-      case 4: return scan_kernel<T, W, 4, FX_Q4, METRIC, true>;
-      case 6: return scan_kernel<T, W, 6, FX_Q6, METRIC, true>;
-      case 8: return scan_kernel<T, W, 8, FX_Q8, METRIC, true>;
-      case 12: return scan_kernel<T, W, 12, FX_Q12, METRIC, true>;
-      case 16: return scan_kernel<T, W, 16, 1, METRIC, true>;
-      default: return scan_kernel<T, W, 24, 1, METRIC, true>;
-    }
+// Slots per lane per row pass (L) the kernels are built for, and the rows in
+// flight per 16-lane group (U) at each, by row type.
+constexpr int kSlotCounts[] = {1, 2, 3, 4, 6, 8, 12, 16, 24};
+constexpr int kNumSlotCounts = sizeof(kSlotCounts) / sizeof(kSlotCounts[0]);
+constexpr int kRows[kNumSlotCounts] = {FX_U1, FX_U2, FX_U3, FX_U4, FX_U6, FX_U8, FX_U12, 1, 1};
+constexpr int kRowsQ8[kNumSlotCounts] = {FX_Q1, FX_Q2, FX_Q3, FX_Q4, FX_Q6, FX_Q8, FX_Q12, 1, 1};
+
+template <typename T>
+constexpr int rows_per_group(int L) {
+  for (int i = 0; i < kNumSlotCounts; ++i)
+    if (kSlotCounts[i] == L) return (sizeof(T) == 1 ? kRowsQ8 : kRows)[i];
+  return 1;
+}
+
+// f(std::integral_constant<int, L>()) for a runtime L of kSlotCounts (any
+// other value: the largest)
+template <int I = 0, typename F>
+static auto with_slots(int L, F&& f) {
+  if constexpr (I + 1 == kNumSlotCounts) {
+    return f(std::integral_constant<int, kSlotCounts[I]>());
   } else {
-    switch (L) {
-      case 1: return scan_kernel<T, W, 1, FX_U1, METRIC, kPipe<T, 1>>;
-      case 2: return scan_kernel<T, W, 2, FX_U2, METRIC, kPipe<T, 2>>;
-      case 3: return scan_kernel<T, W, 3, FX_U3, METRIC, kPipe<T, 3>>;
-      case 4: return scan_kernel<T, W, 4, FX_U4, METRIC, kPipe<T, 4>>;
-      case 6: return scan_kernel<T, W, 6, FX_U6, METRIC, kPipe<T, 6>>;
-      case 8: return scan_kernel<T, W, 8, FX_U8, METRIC, kPipe<T, 8>>;
-      case 12: return scan_kernel<T, W, 12, FX_U12, METRIC, kPipe<T, 12>>;
-      case 16: return scan_kernel<T, W, 16, 1, METRIC, kPipe<T, 16>>;
-      default: return scan_kernel<T, W, 24, 1, METRIC, kPipe<T, 24>>;
-    }
+    return L == kSlotCounts[I] ? f(std::integral_constant<int, kSlotCounts[I]>())
+                               : with_slots<I + 1>(L, f);
   }
 }
 
-template <typename T, int W, int METRIC>
-static ScanKernelFn pick_stream_l(int L) {
-  switch (L) {
-    case 1: return stream_scan_kernel<T, W, 1, FX_U1, METRIC>;
-    case 2: return stream_scan_kernel<T, W, 2, FX_U2, METRIC>;
-    case 3: return stream_scan_kernel<T, W, 3, FX_U3, METRIC>;
-    case 4: return stream_scan_kernel<T, W, 4, FX_U4, METRIC>;
-    case 6: return stream_scan_kernel<T, W, 6, FX_U6, METRIC>;
-    case 8: return stream_scan_kernel<T, W, 8, FX_U8, METRIC>;
-    case 12: return stream_scan_kernel<T, W, 12, FX_U12, METRIC>;
-    case 16: return stream_scan_kernel<T, W, 16, 1, METRIC>;
-    default: return stream_scan_kernel<T, W, 24, 1, METRIC>;
-  }
+ScanKernelFn select_scan_kernel(int dtype, int metric, int W, int L) {
+  return with_kind(dtype, metric, [&](auto kind) -> ScanKernelFn {
+    using K = decltype(kind);
+    using T = typename K::Row;
+    if (W == 1) return scan_kernel<T, 1, 16, 1, K::kMetric, true>;
+    return with_slots(L, [](auto l) -> ScanKernelFn {
+      constexpr int L = decltype(l)::value;
+      return scan_kernel<T, K::kSlot, L, rows_per_group<T>(L), K::kMetric, kPipe<T, L>>;
+    });
+  });
 }
 
-// the streaming kernel for vector-width f32 / f16 rows of exactly 16 * L slots
-static ScanKernelFn select_stream_kernel(int dtype, int metric, int L) {
-  if (dtype == FX_DTYPE_F32) {
-    if (metric == 0) return pick_stream_l<float, 4, 0>(L);
-    if (metric == 1) return pick_stream_l<float, 4, 1>(L);
-    return pick_stream_l<float, 4, 2>(L);
-  }
-  if (metric == 0) return pick_stream_l<_Float16, 8, 0>(L);
-  if (metric == 1) return pick_stream_l<_Float16, 8, 1>(L);
-  return pick_stream_l<_Float16, 8, 2>(L);
+// The kernel for plain scans of vector-width rows of one pass: the stream
+// ring for f32 / f16 rows (of exactly 16 * L slots), the DMA ring for quint8
+// rows of up to 4 slots per lane (null above)
+static ScanKernelFn select_plain_kernel(int dtype, int metric, int L) {
+  return with_kind(dtype, metric, [&](auto kind) -> ScanKernelFn {
+    using K = decltype(kind);
+    using T = typename K::Row;
+    return with_slots(L, [](auto l) -> ScanKernelFn {
+      constexpr int L = decltype(l)::value;
+      if constexpr (sizeof(T) != 1) {
+        return stream_scan_kernel<T, K::kSlot, L, rows_per_group<T>(L), K::kMetric>;
+      } else if constexpr (L <= 4) {
+        return dma_scan_kernel<L, FX_Q8DMA_U, K::kMetric>;
+      } else {
+        return nullptr;
+      }
+    });
+  });
 }
 
 // Classes (dtype, L) whose plain scans stream by default ("scan_stream" -1):
 // those measured faster than the register tiles.
 static bool stream_default(int dtype, int L) {
   return dtype == FX_DTYPE_F32 && L == 12;
-}
-
-template <typename T, int METRIC>
-static ScanKernelFn pick_scalar() {
-  return scan_kernel<T, 1, 16, 1, METRIC, true>;
-}
-
-static int rows_unroll_q8(int L) {
-  switch (L) {
-    case 1: return FX_Q1;
-    case 2: return FX_Q2;
-    case 3: return FX_Q3;
-    case 4: return FX_Q4;
-    case 6: return FX_Q6;
-    case 8: return FX_Q8;
-    case 12: return FX_Q12;
-    default: return 1;
-  }
-}
-
-static int rows_unroll(int L) {
-  switch (L) {
-    case 1: return FX_U1;
-    case 2: return FX_U2;
-    case 3: return FX_U3;
-    case 4: return FX_U4;
-    case 6: return FX_U6;
-    case 8: return FX_U8;
-    case 12: return FX_U12;
-    default: return 1;
-  }
-}
-
-template <int METRIC>
-static ScanKernelFn pick_q8_dma(int L) {
-  constexpr int U = FX_Q8DMA_U;
-  switch (L) {
-    case 1: return scan_kernel<uint8_t, 16, 1, U, METRIC, true, true>;
-    case 2: return scan_kernel<uint8_t, 16, 2, U, METRIC, true, true>;
-    case 3: return scan_kernel<uint8_t, 16, 3, U, METRIC, true, true>;
-    case 4: return scan_kernel<uint8_t, 16, 4, U, METRIC, true, true>;
-    default: return nullptr;
-  }
-}
-
-static ScanKernelFn select_q8_dma_kernel(int metric, int L) {
-  if (metric == 0) return pick_q8_dma<0>(L);
-  if (metric == 1) return pick_q8_dma<1>(L);
-  return pick_q8_dma<2>(L);
-}
-
-ScanKernelFn select_scan_kernel(int dtype, int metric, int W, int L) {
-  if (dtype == FX_DTYPE_F32) {
-    if (W == 1) {
-      if (metric == 0) return pick_scalar<float, 0>();
-      if (metric == 1) return pick_scalar<float, 1>();
-      return pick_scalar<float, 2>();
-    }
-    if (metric == 0) return pick_l<float, 4, 0>(L);
-    if (metric == 1) return pick_l<float, 4, 1>(L);
-    return pick_l<float, 4, 2>(L);
-  }
-  if (dtype == FX_DTYPE_QU8) {
-    if (W == 1) {
-      if (metric == 0) return pick_scalar<uint8_t, 0>();
-      if (metric == 1) return pick_scalar<uint8_t, 1>();
-      return pick_scalar<uint8_t, 2>();
-    }
-    if (metric == 0) return pick_l<uint8_t, 16, 0>(L);
-    if (metric == 1) return pick_l<uint8_t, 16, 1>(L);
-    return pick_l<uint8_t, 16, 2>(L);
-  }
-  if (W == 1) {
-    if (metric == 0) return pick_scalar<_Float16, 0>();
-    if (metric == 1) return pick_scalar<_Float16, 1>();
-    return pick_scalar<_Float16, 2>();
-  }
-  if (metric == 0) return pick_l<_Float16, 8, 0>(L);
-  if (metric == 1) return pick_l<_Float16, 8, 1>(L);
-  return pick_l<_Float16, 8, 2>(L);
 }
 
 // Shape → kernel variant, LDS size, grid.  Pure function of (shape, device).
@@ -1007,16 +866,16 @@ int plan_scan(int64_t n, int64_t d, int dtype, int64_t k, int metric, bool align
     L = 16;
   } else {
     const int64_t need = (S + 15) / 16;
-    static const int choices[] = {1, 2, 3, 4, 6, 8, 12, 16, 24};
-    L = 24;
-    for (int c : choices) {
+    L = kSlotCounts[kNumSlotCounts - 1];
+    for (int c : kSlotCounts) {
       if (c >= need) {
         L = c;
         break;
       }
     }
   }
-  const int U = W == 1 ? 1 : dtype == FX_DTYPE_QU8 ? rows_unroll_q8(L) : rows_unroll(L);
+  const bool qu8 = dtype == FX_DTYPE_QU8;
+  const int U = W == 1 ? 1 : qu8 ? rows_per_group<uint8_t>(L) : rows_per_group<float>(L);
   const int64_t CH = 16 * (int64_t)L;
   const int64_t nch = (S + CH - 1) / CH;
   const size_t qbytes = (size_t)((nch * CH * W * 4 + 15) / 16 * 16);
@@ -1029,22 +888,24 @@ int plan_scan(int64_t n, int64_t d, int dtype, int64_t k, int metric, bool align
     return FX_EUNSUPPORTED;
   }
   p->fn = select_scan_kernel(dtype, metric, W, L);
-  p->fn_dma = nullptr;
-  p->smem_dma = 0;
-  if (dtype == FX_DTYPE_QU8 && W == 16 && nch == 1 && U % FX_Q8DMA_U == 0) {
+  // Plain scans (no mask, no row list) of one-pass rows take their own kernel:
+  // quint8 rows the DMA ring where its tiles fit beside the lists, f32 / f16
+  // rows that fill their 16 * L slots exactly the stream ring where
+  // stream_default says so (same LDS).  The "q8_dma" and "scan_stream"
+  // options (test switches) override.
+  p->fn_plain = nullptr;
+  p->smem_plain = smem;
+  p->plain_name = qu8 ? "dma_scan_kernel" : "stream_scan_kernel";
+  if (qu8 && W == 16 && nch == 1 && U % FX_Q8DMA_U == 0) {
     const size_t sd = smem + (size_t)4 * FX_Q8DMA_STAGES * FX_Q8DMA_U * L * 1024;
     if (sd <= 80 * 1024 && option(kOptQ8Dma) != 0) {  // >= 2 workgroups per CU
-      p->fn_dma = select_q8_dma_kernel(metric, L);
-      p->smem_dma = sd;
+      p->fn_plain = select_plain_kernel(dtype, metric, L);
+      p->smem_plain = sd;
     }
-  }
-  // Plain scans of f32 / f16 rows that fill their 16 * L slots exactly go
-  // through the streaming kernel where stream_default says so; the
-  // "scan_stream" option (test switch) overrides.  Same LDS, same grid.
-  p->fn_stream = nullptr;
-  if (dtype != FX_DTYPE_QU8 && W > 1 && S == CH) {
+  } else if (!qu8 && W > 1 && S == CH) {
     const int64_t o = option(kOptScanStream);
-    if (o < 0 ? stream_default(dtype, L) : o != 0) p->fn_stream = select_stream_kernel(dtype, metric, L);
+    if (o < 0 ? stream_default(dtype, L) : o != 0)
+      p->fn_plain = select_plain_kernel(dtype, metric, L);
   }
   p->W = W;
   p->L = L;
@@ -1062,20 +923,17 @@ int plan_scan(int64_t n, int64_t d, int dtype, int64_t k, int metric, bool align
   if (device) {
     rc = device_cus(&cus);
     if (rc) return rc;
-    // (the streaming kernel needs fewer registers than the tiles: its own limit)
-    rc = kernel_occupancy((const void*)(p->fn_stream != nullptr ? p->fn_stream : p->fn), 256, smem,
-                          &occ);
+    // (the stream ring needs fewer registers than the tiles: its own limit)
+    rc = kernel_occupancy((const void*)(p->fn_plain != nullptr && !qu8 ? p->fn_plain : p->fn), 256,
+                          smem, &occ);
     if (rc) return rc;
   } else {
     cus = 256;
     occ = 1 << 20;
   }
-  if (device && p->fn_dma != nullptr) {  // one grid serves both variants: the smaller occupancy
+  if (device && p->fn_plain != nullptr && qu8) {  // one grid serves tiles and DMA ring: the smaller occupancy
     int occ2 = 0;
-    // the DMA variants may take more than the default 64 KB of dynamic LDS
-    rc = allow_lds((const void*)p->fn_dma);
-    if (rc) return rc;
-    rc = kernel_occupancy((const void*)p->fn_dma, 256, p->smem_dma, &occ2);
+    rc = kernel_occupancy((const void*)p->fn_plain, 256, p->smem_plain, &occ2);
     if (rc) return rc;
     if (occ2 < occ) occ = occ2;
   }
@@ -1085,7 +943,7 @@ int plan_scan(int64_t n, int64_t d, int dtype, int64_t k, int metric, bool align
   // Rows of >= 12 slots per lane (768-d f32, 1536-d f16 and longer): one
   // block per CU reads as fast or faster (1536-d f16: 4.50 vs 4.66 ms).
   const int cap_occ =
-      diag_env("FX_SCAN_BLOCKS_PER_CU", dtype == FX_DTYPE_QU8 ? 3 : L >= 12 ? 1 : 2);
+      diag_env("FX_SCAN_BLOCKS_PER_CU", qu8 ? 3 : L >= 12 ? 1 : 2);
   if (cap_occ > 0 && cap_occ < occ) occ = cap_occ;
   if (occ < 1) occ = 1;
   const int64_t max_blocks = (int64_t)cus * occ;
@@ -1136,22 +994,16 @@ void limit_scan_blocks(ScanPlan* p, int64_t n, int64_t max_blocks) {
 
 int launch_scan(const ScanPlan& p, const ScanArgs& a, int64_t nq, hipStream_t stream) {
   dim3 grid((unsigned)p.blocks, (unsigned)nq);
-  if (p.fn_dma != nullptr && a.mask == nullptr && a.rows == nullptr) {
-    if (int rc = allow_lds((const void*)p.fn_dma)) return rc;
-    ScanArgs b = a;
-    b.interleave = p.interleave & 1;
-    hipLaunchKernelGGL(p.fn_dma, grid, dim3(256), p.smem_dma, stream, b);
-    return check_launch("scan_kernel (quint8 LDS-DMA)");
-  }
-  const bool stream_fn = p.fn_stream != nullptr && a.mask == nullptr && a.rows == nullptr;
-  const ScanKernelFn fn = stream_fn ? p.fn_stream : p.fn;
-  if (p.smem > 64 * 1024) {
+  const bool plain = p.fn_plain != nullptr && a.mask == nullptr && a.rows == nullptr;
+  const ScanKernelFn fn = plain ? p.fn_plain : p.fn;
+  const size_t smem = plain ? p.smem_plain : p.smem;
+  if (smem > 64 * 1024) {
     if (int rc = allow_lds((const void*)fn)) return rc;
   }
   ScanArgs b = a;
   b.interleave = p.interleave;
-  hipLaunchKernelGGL(fn, grid, dim3(256), p.smem, stream, b);
-  return check_launch(stream_fn ? "stream_scan_kernel" : "scan_kernel");
+  hipLaunchKernelGGL(fn, grid, dim3(256), smem, stream, b);
+  return check_launch(plain ? p.plain_name : "scan_kernel");
 }
 
 }  // namespace fx
