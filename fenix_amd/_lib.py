@@ -87,6 +87,12 @@ SYMBOLS = (
     "fx_knn_scan_img8_ex",
     "fx_knn_reduce_img8_ex",
     "fx_knn_search_img8_ex",
+    "fx_qmask_words",
+    "fx_qmask_pack",
+    "fx_qmask_filter_used",
+    "fx_knn_scan_qmask_ex",
+    "fx_knn_reduce_qmask_ex",
+    "fx_knn_search_qmask_ex",
     "fx_comm_init_all",
     "fx_comm_destroy",
     "fx_allgather_topk",
@@ -101,7 +107,7 @@ SYMBOLS = (
 OPTIONS = ("batched", "batch_min_queries", "batch_cap", "batch_sample_ratio", "force_fallback",
            "scan_interleave", "q8_dma", "filter_image", "batch_ub_test", "single_query_image",
            "i8_max_k", "img6", "img8", "i8_sample_ratio", "i8_grow_ratio", "select_prune",
-           "scan_stream", "filter_hold", "qu8_batch_min_work")
+           "scan_stream", "filter_hold", "qu8_batch_min_work", "qmask_batch_min_ratio")
 
 _lock = threading.Lock()
 _lib = None
@@ -244,6 +250,20 @@ def load() -> ctypes.CDLL:
         L.fx_knn_reduce_img8_ex.restype = ci
         L.fx_knn_search_img8_ex.argtypes = [pc_, vp, vp, vp, i64, ci, i64, vp, vp, sz, vp, vp, vp]
         L.fx_knn_search_img8_ex.restype = ci
+        L.fx_qmask_words.argtypes = [i64]
+        L.fx_qmask_words.restype = i64
+        L.fx_qmask_pack.argtypes = [vp, i64, i64, i64, vp, vp]
+        L.fx_qmask_pack.restype = ci
+        L.fx_qmask_filter_used.argtypes = [i64, i64, ci, i64, i64, ci, ctypes.POINTER(ci)]
+        L.fx_qmask_filter_used.restype = ci
+        L.fx_knn_scan_qmask_ex.argtypes = [pc_, vp, vp, vp, i64, ci, i64, vp, i64, vp, vp, sz, vp]
+        L.fx_knn_scan_qmask_ex.restype = ci
+        L.fx_knn_reduce_qmask_ex.argtypes = [pc_, vp, vp, i64, ci, i64, vp, i64, vp, vp, sz, vp,
+                                             vp, vp]
+        L.fx_knn_reduce_qmask_ex.restype = ci
+        L.fx_knn_search_qmask_ex.argtypes = [pc_, vp, vp, vp, i64, ci, i64, vp, i64, vp, vp, sz,
+                                             vp, vp, vp]
+        L.fx_knn_search_qmask_ex.restype = ci
         L.fx_comm_init_all.argtypes = [ci, ctypes.POINTER(ci), ctypes.POINTER(vp)]
         L.fx_comm_init_all.restype = ci
         L.fx_comm_destroy.argtypes = [vp]
@@ -323,6 +343,25 @@ def filter_image_used(n: int, d: int, dtype: int, nq: int, k: int, metric: int) 
         return bool(out.value)
 
     return _planned(("img", n, d, dtype, nq, k, metric), compute)
+
+
+def qmask_words(nq: int) -> int:
+    """fx_qmask_words: uint32 words per row of fx_qmask_pack's bit matrix."""
+    return int(load().fx_qmask_words(nq))
+
+
+def qmask_filter_used(n: int, d: int, dtype: int, nq: int, k: int, metric: int) -> int:
+    """fx_qmask_filter_used: the slice width (64 or 128) when a search of this
+    shape with per-query row masks runs the int8 filter, 0 when it scans
+    exactly (also for k above the fused scan's: such a batch is not served)."""
+    def compute() -> int:
+        if k > max_k():
+            return 0
+        out = ctypes.c_int(0)
+        check(load().fx_qmask_filter_used(n, d, dtype, nq, k, metric, ctypes.byref(out)))
+        return int(out.value)
+
+    return _planned(("qmask", n, d, dtype, nq, k, metric), compute)
 
 
 def image8_perm(n: int) -> int:

@@ -17,8 +17,12 @@ batch runs with the largest k asked for and each request gets the prefix of
 its own length (a top-K list sorted by (distance, row) starts with the top-k
 for every k <= K).  An exception in a batch is raised in every request of it.
 
-Only the plain case is coalesced (one query, no filter mask, no probe set);
-``FENIX_AMD_COALESCE=0`` turns it off.  The module is torch-free so its
+A request may carry a payload (``extra``: a filtered or probe search's
+per-shard row masks and kept-row counts).  A batch in which any request has
+one is run as ``run(queries, K, extras)`` (None standing for the plain
+requests) and holds at most ``MASKED_MAX`` requests, one 128-query slice of
+the per-query-mask filter; a batch of plain requests runs ``run(queries, K)``
+as before.  ``FENIX_AMD_COALESCE=0`` turns coalescing off.  The module is torch-free so its
 bookkeeping is tested on the CPU with a stand-in search function.
 """
 
@@ -32,7 +36,11 @@ import numpy as np
 
 # run(queries [n, d] float32, K) -> (dist [n, K], rows [n, K], ...): every
 # returned array is indexed [query, rank, ...] and sliced per request
-RunFn = Callable[[np.ndarray, int], Tuple[np.ndarray, ...]]
+# (a batch with payloads: run(queries, K, extras [n]), see the module text)
+RunFn = Callable[..., Tuple[np.ndarray, ...]]
+
+# requests per batch when any of them carries a payload
+MASKED_MAX = 128
 
 
 def enabled() -> bool:
@@ -40,11 +48,12 @@ def enabled() -> bool:
 
 
 class _Request:
-    __slots__ = ("query", "k", "wake", "promoted", "parts", "error")
+    __slots__ = ("query", "k", "extra", "wake", "promoted", "parts", "error")
 
-    def __init__(self, query: np.ndarray, k: int) -> None:
+    def __init__(self, query: np.ndarray, k: int, extra: Any = None) -> None:
         self.query = query
         self.k = k
+        self.extra = extra
         self.wake = threading.Event()  # result ready, or promoted to leader
         self.promoted = False
         self.parts: Optional[Tuple[np.ndarray, ...]] = None
@@ -69,9 +78,9 @@ class Coalescer:
         self.batches = 0   # statistics (tests, tools/bench_flight.py)
         self.requests = 0
 
-    def search(self, key: Hashable, run: RunFn, query: np.ndarray, k: int
+    def search(self, key: Hashable, run: RunFn, query: np.ndarray, k: int, extra: Any = None
                ) -> Tuple[np.ndarray, ...]:
-        req = _Request(np.ascontiguousarray(query, dtype=np.float32).reshape(-1), int(k))
+        req = _Request(np.ascontiguousarray(query, dtype=np.float32).reshape(-1), int(k), extra)
         with self._lock:
             self.requests += 1
             self._queues.setdefault(key, []).append(req)
@@ -95,7 +104,10 @@ class Coalescer:
     def _lead_once(self, key: Hashable, run: RunFn) -> None:
         with self._lock:
             queue = self._queues.get(key, [])
-            batch, rest = queue[: self.max_batch], queue[self.max_batch :]
+            take = self.max_batch
+            if any(r.extra is not None for r in queue[:take]):
+                take = min(take, MASKED_MAX)
+            batch, rest = queue[:take], queue[take:]
             self._queues[key] = rest
             self.batches += 1
         self._run(batch, run)
@@ -112,7 +124,11 @@ class Coalescer:
     def _run(batch: List[_Request], run: RunFn) -> None:
         try:
             kmax = max(r.k for r in batch)
-            parts = run(np.stack([r.query for r in batch]), kmax)
+            queries = np.stack([r.query for r in batch])
+            if any(r.extra is not None for r in batch):
+                parts = run(queries, kmax, [r.extra for r in batch])
+            else:
+                parts = run(queries, kmax)
             for i, r in enumerate(batch):
                 r.parts = tuple(p[i : i + 1, : r.k] for p in parts)
         except BaseException as e:  # every request of the batch sees the failure

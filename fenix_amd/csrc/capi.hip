@@ -14,7 +14,7 @@ static std::atomic<uint64_t> g_host_syncs{0};
 // The fallback scan's arguments: top-k lists into ws, each workgroup gated
 // on its query's count (> gate_cap: recompute)
 static ScanArgs fallback_args(const SearchLayout& s, const fx_corpus& c, int64_t k,
-                              const uint32_t* mask, int64_t gate_cap, char* ws) {
+                              const RowMasks& mask, int64_t gate_cap, char* ws) {
   ScanArgs a = scan_args(s.scan, c, nullptr, 0, mask, k, kModeTopk);
   a.out_lists = reinterpret_cast<uint64_t*>(ws);
   a.gate_cap = gate_cap;
@@ -24,7 +24,7 @@ static ScanArgs fallback_args(const SearchLayout& s, const fx_corpus& c, int64_t
 // The fallback's gated scan alone over all nq queries (s.fb_queries >= nq):
 // per overflowing query nlists lists of k composites at *lists, [nq][nlists k]
 static int fallback_scan(const SearchLayout& s, const fx_corpus& c, const float* queries,
-                         int64_t nq, int64_t k, const uint32_t* mask, const uint32_t* count,
+                         int64_t nq, int64_t k, const RowMasks& mask, const uint32_t* count,
                          int64_t gate_cap, char* ws, hipStream_t st, const uint64_t** lists) {
   ScanArgs a = fallback_args(s, c, k, mask, gate_cap, ws);
   a.q = queries;
@@ -40,13 +40,14 @@ static int fallback_scan(const SearchLayout& s, const fx_corpus& c, const float*
 // overflow, so nothing waits for the host; the merge writes only the
 // recomputed queries' results.
 static int fallback_search(const SearchLayout& s, const fx_corpus& c, const float* queries,
-                           int64_t nq, int64_t k, const uint32_t* mask, const uint32_t* count,
+                           int64_t nq, int64_t k, const RowMasks& mask, const uint32_t* count,
                            int64_t gate_cap, char* ws, float* out_dist, int64_t* out_row,
                            hipStream_t st) {
   ScanArgs a = fallback_args(s, c, k, mask, gate_cap, ws);
   for (int64_t q0 = 0; q0 < nq; q0 += s.fb_queries) {
     const int64_t qn = (nq - q0) < s.fb_queries ? (nq - q0) : s.fb_queries;
     a.q = queries + (size_t)q0 * c.d;
+    a.mask = mask.from_query(q0).mask;  // (per-query masks: the round's first query's)
     a.gate = count + (size_t)q0 * kCountStride;
     int rc = launch_scan(s.scan, a, qn, st);
     if (rc) return rc;
@@ -164,10 +165,20 @@ static int filter_phases(const BatchLayout& b, const fx_corpus& c, const void* i
 // image8_qu8_kernel, knn_filter.hip).  IP and cosine take the queries as they are.
 static constexpr int64_t kI8RescoreAllMaxQ = 2;
 
+// Per-query row masks (mask.qstride != 0; the plan's BatchLayout::qmask): every
+// filter pass tests the pair's admission bit from the packed matrix
+// mask.qmask (launch_filter: filter_img6_kernel<., true>); the selects, the
+// gate and the rescoring see only appended candidates.
 static int filter_phases_i8(const BatchLayout& b, const fx_corpus& c, const void* image,
                             const float* rowinfo, const float* Q, int64_t nq, int metric,
-                            int64_t k, const uint32_t* mask, void* ws, hipStream_t st) {
+                            int64_t k, const RowMasks& mask, void* ws, hipStream_t st) {
   const BatchWorkspace w(b, ws);
+  const bool per_query = mask.qstride != 0;
+  if (per_query && (!b.qmask || mask.qmask == nullptr || (uintptr_t)mask.qmask % 16 != 0 ||
+                    mask.qwords < qmask_words(nq))) {
+    set_error("per-query masks: no packed bit matrix (fx_qmask_pack), or not 16-byte aligned");
+    return FX_EINVAL;
+  }
   const Quant z = {c.scale, (float)c.zero_point};
   const int d = (int)c.d;
   const int64_t nq_pad8 = (nq + 255) / 256 * 256;
@@ -202,7 +213,9 @@ static int filter_phases_i8(const BatchLayout& b, const fx_corpus& c, const void
     a.perm_a = image8_perm(c.n);
     a.qinfo = w.qinfo;
     a.nq = nq;
-    a.mask = mask;
+    a.mask = per_query ? nullptr : mask.mask;
+    a.qmask = per_query ? mask.qmask : nullptr;
+    a.qmask_words = per_query ? mask.qwords : 0;
     a.tile_start = b.start[ph];
     a.tile_stride = b.stride[ph];
     a.num_tiles = b.num[ph];
@@ -319,11 +332,15 @@ int fx_knn_workspace_bytes_img8(int64_t n, int64_t d, int dtype, int64_t nq, int
     for (int aligned = 0; aligned < 2; ++aligned) {
       // with an int8 image a search may still plan without it (k above
       // i8_max_k): the larger of both; without one, the image-free plan only
+      // (and a search with per-query masks may plan exact where the plain
+      // one plans the filter)
       for (int with8 = 0; with8 < (img8 ? 2 : 1); ++with8) {
-        SearchLayout s;
-        rc = plan_search(n, d, dtype, nq, k, metric, aligned != 0, with8 != 0, &s);
-        if (rc) return rc;
-        if (s.total > best) best = s.total;
+        for (int qm = 0; qm < 2; ++qm) {
+          SearchLayout s;
+          rc = plan_search(n, d, dtype, nq, k, metric, aligned != 0, with8 != 0, &s, qm != 0);
+          if (rc) return rc;
+          if (s.total > best) best = s.total;
+        }
       }
     }
   }
@@ -339,7 +356,8 @@ int fx_knn_workspace_bytes_img8(int64_t n, int64_t d, int dtype, int64_t nq, int
 // entry point takes quint8 codes (a descriptor with their scale and zero
 // point, or a call that only reads the plan).
 static int search_layout(const fx_corpus& c, int64_t nq, int metric, int64_t k, bool img8,
-                         const void* ws, size_t ws_bytes, SearchLayout* s, bool qu8 = false) {
+                         const void* ws, size_t ws_bytes, SearchLayout* s, bool qu8 = false,
+                         bool qmask = false) {
   int rc = validate(c.n, c.d, c.dtype, nq, k, metric, qu8);
   if (rc) return rc;
   rc = validate_quant(c);
@@ -348,7 +366,8 @@ static int search_layout(const fx_corpus& c, int64_t nq, int metric, int64_t k, 
     set_error("null pointer argument");
     return FX_EINVAL;
   }
-  rc = plan_search(c.n, c.d, c.dtype, nq, k, metric, ((uintptr_t)c.data % 16) == 0, img8, s);
+  rc = plan_search(c.n, c.d, c.dtype, nq, k, metric, ((uintptr_t)c.data % 16) == 0, img8, s,
+                   qmask);
   if (rc) return rc;
   if (ws_bytes < s->total) {
     set_error("workspace too small: %zu < %zu", ws_bytes, s->total);
@@ -367,7 +386,7 @@ static bool image_applies(const SearchLayout& s, const fx_corpus& c, bool img8) 
 
 static int scan_impl(const SearchLayout& s, const fx_corpus& c, const void* image,
                      const float* rowinfo, bool img8, const float* queries, int64_t nq,
-                     int metric, int64_t k, const uint32_t* mask, void* ws, hipStream_t st) {
+                     int metric, int64_t k, const RowMasks& mask, void* ws, hipStream_t st) {
   if (!queries) {
     set_error("null pointer argument");
     return FX_EINVAL;
@@ -389,8 +408,12 @@ static int scan_impl(const SearchLayout& s, const fx_corpus& c, const void* imag
       set_error("quint8 batch without an int8 filter image");
       return FX_EINVAL;
     }
-    return filter_phases(s.batch, c, img ? image : nullptr, rowinfo, queries, nq, metric, k, mask,
-                         ws, st);
+    if (mask.qstride != 0) {  // (unreachable: per-query masks plan an int8 image or exact)
+      set_error("per-query masks without an int8 filter image");
+      return FX_EINVAL;
+    }
+    return filter_phases(s.batch, c, img ? image : nullptr, rowinfo, queries, nq, metric, k,
+                         mask.mask, ws, st);
   }
   char* w = reinterpret_cast<char*>(ws);
   if (s.large) {
@@ -407,17 +430,18 @@ static int scan_impl(const SearchLayout& s, const fx_corpus& c, const void* imag
 // The scan half of a search call: plan, then run (fx_knn_scan*)
 static int scan_call(const fx_corpus& c, const void* image, const float* rowinfo, bool img8,
                      const float* queries, int64_t nq, int metric, int64_t k,
-                     const uint32_t* mask, void* ws, size_t ws_bytes, void* stream,
+                     const RowMasks& mask, void* ws, size_t ws_bytes, void* stream,
                      bool qu8 = false) {
   SearchLayout s;
-  int rc = search_layout(c, nq, metric, k, img8 && image != nullptr, ws, ws_bytes, &s, qu8);
+  int rc = search_layout(c, nq, metric, k, img8 && image != nullptr, ws, ws_bytes, &s, qu8,
+                         mask.qstride != 0);
   if (rc) return rc;
   return scan_impl(s, c, image, rowinfo, img8, queries, nq, metric, k, mask, ws,
                    reinterpret_cast<hipStream_t>(stream));
 }
 
 static int reduce_impl(const SearchLayout& s, const fx_corpus& c, const float* queries,
-                       int64_t nq, int64_t k, const uint32_t* mask, void* ws, float* out_dist,
+                       int64_t nq, int64_t k, const RowMasks& mask, void* ws, float* out_dist,
                        int64_t* out_row, hipStream_t st) {
   if (!out_dist || !out_row) {
     set_error("null pointer argument");
@@ -459,10 +483,10 @@ static int reduce_impl(const SearchLayout& s, const fx_corpus& c, const float* q
 // The reduce half of a search call (fx_knn_reduce*): its own plan, which
 // equals the scan half's as long as no option changed in between
 static int reduce_call(const fx_corpus& c, bool img8, const float* queries, int64_t nq, int metric,
-                       int64_t k, const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
+                       int64_t k, const RowMasks& mask, void* ws, size_t ws_bytes, float* out_dist,
                        int64_t* out_row, void* stream, bool qu8 = false) {
   SearchLayout s;
-  int rc = search_layout(c, nq, metric, k, img8, ws, ws_bytes, &s, qu8);
+  int rc = search_layout(c, nq, metric, k, img8, ws, ws_bytes, &s, qu8, mask.qstride != 0);
   if (rc) return rc;
   return reduce_impl(s, c, queries, nq, k, mask, ws, out_dist, out_row,
                      reinterpret_cast<hipStream_t>(stream));
@@ -471,14 +495,15 @@ static int reduce_call(const fx_corpus& c, bool img8, const float* queries, int6
 // A whole search (fx_knn_search*): one plan runs both halves
 static int search_call(const fx_corpus& c, const void* image, const float* rowinfo, bool img8,
                        const float* queries, int64_t nq, int metric, int64_t k,
-                       const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
+                       const RowMasks& mask, void* ws, size_t ws_bytes, float* out_dist,
                        int64_t* out_row, void* stream, bool qu8 = false) {
   if (!out_dist || !out_row) {
     set_error("null pointer argument");
     return FX_EINVAL;
   }
   SearchLayout s;
-  int rc = search_layout(c, nq, metric, k, img8 && image != nullptr, ws, ws_bytes, &s, qu8);
+  int rc = search_layout(c, nq, metric, k, img8 && image != nullptr, ws, ws_bytes, &s, qu8,
+                         mask.qstride != 0);
   if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   rc = scan_impl(s, c, image, rowinfo, img8, queries, nq, metric, k, mask, ws, st);
@@ -773,6 +798,94 @@ int fx_knn_search_img8_ex(const fx_corpus* c, const void* image, const float* ro
   if (!checked_corpus(c)) return FX_EINVAL;
   return search_call(*c, image, rowinfo, true, queries, nq, metric, k, mask, ws, ws_bytes,
                      out_dist, out_row, stream, true);
+}
+
+// Per-query row masks (include/fenix_knn.h "Per-query row masks"): the
+// *_img8_ex triple with every query's own bitmap, masks + q * mask_stride, and
+// their packed bit matrix (fx_qmask_pack) for the filter passes.  masks NULL:
+// every query admits every row (the plain search).
+int64_t fx_qmask_words(int64_t nq) { return qmask_words(nq); }
+
+int fx_qmask_pack(const uint32_t* masks, int64_t mask_stride, int64_t nq, int64_t n, uint32_t* out,
+                  void* stream) {
+  if (nq < 1 || n < 1 || n >= 0xffffffffll || mask_stride < (n + 31) / 32) {
+    set_error("fx_qmask_pack: nq=%lld n=%lld mask_stride=%lld", (long long)nq, (long long)n,
+              (long long)mask_stride);
+    return FX_EINVAL;
+  }
+  if (!masks || !out || (uintptr_t)out % 16 != 0) {
+    set_error("fx_qmask_pack: null pointer argument, or out not 16-byte aligned");
+    return FX_EINVAL;
+  }
+  return launch_qmask_pack(masks, mask_stride, nq, n, out, reinterpret_cast<hipStream_t>(stream));
+}
+
+static int qmask_row_masks(const fx_corpus* c, const uint32_t* masks, int64_t mask_stride,
+                           const uint32_t* qmask, int64_t nq, int64_t k, RowMasks* m) {
+  if (!checked_corpus(c)) return FX_EINVAL;
+  if (k > kMaxK) {
+    set_error("per-query masks: k=%lld outside [1, %lld]", (long long)k, (long long)kMaxK);
+    return FX_EUNSUPPORTED;
+  }
+  *m = RowMasks();
+  if (masks == nullptr) return FX_OK;
+  if (mask_stride < (c->n + 31) / 32 || mask_stride > 0x7fffffffll) {
+    set_error("per-query masks: mask_stride=%lld below the %lld words of a bitmap",
+              (long long)mask_stride, (long long)((c->n + 31) / 32));
+    return FX_EINVAL;
+  }
+  m->mask = masks;
+  m->qstride = mask_stride;
+  m->qmask = qmask;
+  m->qwords = qmask_words(nq);
+  return FX_OK;
+}
+
+int fx_qmask_filter_used(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, int metric,
+                         int* out) {
+  if (!out) {
+    set_error("null pointer argument");
+    return FX_EINVAL;
+  }
+  *out = 0;
+  int rc = validate(n, d, dtype, nq, k, metric, true);
+  if (rc) return rc;
+  SearchLayout s;
+  rc = plan_search(n, d, dtype, nq, k, metric, true, option(kOptFilterImage) == 8, &s, true);
+  if (rc) return rc;
+  if (s.batched && s.batch.qmask) *out = filter_qmask_kind(s.batch.dq, nq);
+  return FX_OK;
+}
+
+int fx_knn_scan_qmask_ex(const fx_corpus* c, const void* image, const float* rowinfo,
+                         const float* queries, int64_t nq, int metric, int64_t k,
+                         const uint32_t* masks, int64_t mask_stride, const uint32_t* qmask,
+                         void* ws, size_t ws_bytes, void* stream) {
+  RowMasks m;
+  if (int rc = qmask_row_masks(c, masks, mask_stride, qmask, nq, k, &m)) return rc;
+  return scan_call(*c, image, rowinfo, true, queries, nq, metric, k, m, ws, ws_bytes, stream,
+                   true);
+}
+
+int fx_knn_reduce_qmask_ex(const fx_corpus* c, const void* image, const float* queries,
+                           int64_t nq, int metric, int64_t k, const uint32_t* masks,
+                           int64_t mask_stride, const uint32_t* qmask, void* ws, size_t ws_bytes,
+                           float* out_dist, int64_t* out_row, void* stream) {
+  RowMasks m;
+  if (int rc = qmask_row_masks(c, masks, mask_stride, qmask, nq, k, &m)) return rc;
+  return reduce_call(*c, image != nullptr, queries, nq, metric, k, m, ws, ws_bytes, out_dist,
+                     out_row, stream, true);
+}
+
+int fx_knn_search_qmask_ex(const fx_corpus* c, const void* image, const float* rowinfo,
+                           const float* queries, int64_t nq, int metric, int64_t k,
+                           const uint32_t* masks, int64_t mask_stride, const uint32_t* qmask,
+                           void* ws, size_t ws_bytes, float* out_dist, int64_t* out_row,
+                           void* stream) {
+  RowMasks m;
+  if (int rc = qmask_row_masks(c, masks, mask_stride, qmask, nq, k, &m)) return rc;
+  return search_call(*c, image, rowinfo, true, queries, nq, metric, k, m, ws, ws_bytes, out_dist,
+                     out_row, stream, true);
 }
 
 // merges of lists longer than the fused path's k go through the radix sort

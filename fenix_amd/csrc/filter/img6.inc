@@ -40,16 +40,31 @@ struct Img6Shared {
   uint32_t seg[fBQ + 3 * fBQ * kI6SEG];
   uint32_t segbase[fBQ];
 };
+// The QMASK build (per-query row masks, FilterArgs::qmask): each row's slice
+// of query bits beside its terms, fBQ / 32 words per row
+constexpr int kI6QW = fBQ / 32;
+typedef uint32_t i6_qbits __attribute__((ext_vector_type(kI6QW)));
+struct Img6SharedQ : Img6Shared {
+  i6_qbits rqmask[kI6BM];
+};
 // the query slice follows: (dq / 64) chunks x 128 queries x 64 B
-static size_t img6_smem(int dq) { return sizeof(Img6Shared) + (size_t)(dq / 64) * fBQ * 64; }
+static size_t img6_smem(int dq, bool qmask = false) {
+  return (qmask ? sizeof(Img6SharedQ) : sizeof(Img6Shared)) + (size_t)(dq / 64) * fBQ * 64;
+}
 bool img6_fits(int dq) { return img6_smem(dq) <= 160 * 1024; }
+bool img6_fits_qmask(int dq) { return img6_smem(dq, true) <= 160 * 1024; }
 
-template <int METRIC>
+// QMASK: a (row, query) pair is appended only where bit q of the row's words
+// a.qmask[crow * a.qmask_words ..] is set (fx_qmask_pack's matrix, indexed by
+// CORPUS row like a.mask); a row no query of the slice admits is skipped like
+// a row the shared mask excludes.
+template <int METRIC, bool QMASK = false>
 __global__ void __launch_bounds__(kI6Threads, 1) filter_img6_kernel(FilterArgs a) {
   constexpr int XS = FX_I6_XS, SEG = kI6SEG;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  Img6Shared* sh = reinterpret_cast<Img6Shared*>(smem);
-  unsigned char* qslice = smem + sizeof(Img6Shared);
+  using Shared = std::conditional_t<QMASK, Img6SharedQ, Img6Shared>;
+  Shared* sh = reinterpret_cast<Shared*>(smem);
+  unsigned char* qslice = smem + sizeof(Shared);
 #ifdef FX_DIAG_BUILD
   const int diag = a.diag;
 #else
@@ -185,6 +200,10 @@ __global__ void __launch_bounds__(kI6Threads, 1) filter_img6_kernel(FilterArgs a
     const f32x4 rsum = *reinterpret_cast<const f32x4*>(a.rowinfo + rowc * kI8RowInfo);
     const uint32_t crow = perm_row(a.perm_a, a.n, rowc);
     const uint32_t mword = a.mask != nullptr ? a.mask[crow >> 5] >> (crow & 31) : 1u;
+    i6_qbits qm = i6_qbits(0u);  // the row's query bits of this slice (crow < n: in bounds)
+    if constexpr (QMASK)
+      qm = *reinterpret_cast<const i6_qbits*>(a.qmask + (int64_t)crow * a.qmask_words +
+                                              (int64_t)blockIdx.y * kI6QW);
     // k-step groups of XS: the first starts the accumulators, the last
     // refills from the next tile
     for (int g = 0; g < ngroups; ++g) {
@@ -200,7 +219,14 @@ __global__ void __launch_bounds__(kI6Threads, 1) filter_img6_kernel(FilterArgs a
     if (lane < 4) sh->rflags[(lane >> 1) * 16 + wid * 2 + (lane & 1)] = 0u;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (h == 0) {
-      const bool ok = row < a.n && (mword & 1u);
+      bool ok = row < a.n && (mword & 1u);
+      if constexpr (QMASK) {
+        uint32_t anyq = 0u;
+#pragma unroll
+        for (int u = 0; u < kI6QW; ++u) anyq |= qm[u];
+        ok = ok && anyq != 0u;
+        sh->rqmask[lr] = qm;
+      }
       const float y1 = METRIC == 1 ? rsum[1] : METRIC == 2 ? rsum[2] : rsum[3];
       i8_note_row(sh->rinfo, sh->rterm, sh->rext, sh->rflags, lr, rsum[0], y1, rsum[1], ok);
       sh->rrow[lr] = (uint32_t)a.row_base + crow;
@@ -226,9 +252,15 @@ __global__ void __launch_bounds__(kI6Threads, 1) filter_img6_kernel(FilterArgs a
                    "memory");
     else
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (!(diag & 2))
-      i8_epilogue<METRIC>(acc, sh->rinfo, sh->rterm, sh->rext, sh->rrow, sh->rflags, sh->qtab,
-                          sh->qinf, a, q0, wid, h, l32, sh->seg, diag, segcap);
+    if (!(diag & 2)) {
+      if constexpr (QMASK)
+        i8_epilogue<METRIC, true>(acc, sh->rinfo, sh->rterm, sh->rext, sh->rrow, sh->rflags,
+                                  sh->qtab, sh->qinf, a, q0, wid, h, l32, sh->seg, diag, segcap,
+                                  reinterpret_cast<const uint32_t*>(sh->rqmask));
+      else
+        i8_epilogue<METRIC>(acc, sh->rinfo, sh->rterm, sh->rext, sh->rrow, sh->rflags, sh->qtab,
+                            sh->qinf, a, q0, wid, h, l32, sh->seg, diag, segcap);
+    }
     xr = xn;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -237,9 +269,19 @@ __global__ void __launch_bounds__(kI6Threads, 1) filter_img6_kernel(FilterArgs a
 
 int launch_img6(const FilterArgs& a, int metric, hipStream_t stream) {
   if (a.num_tiles <= 0) return FX_OK;
-  const void* fn = metric == FX_METRIC_COS  ? (const void*)filter_img6_kernel<2>
-                   : metric == FX_METRIC_IP ? (const void*)filter_img6_kernel<1>
-                                            : (const void*)filter_img6_kernel<0>;
+  const bool qm = a.qmask != nullptr;
+  if (qm && (a.qmask_words < (a.nq + fBQ - 1) / fBQ * kI6QW || a.qmask_words % 4 != 0)) {
+    set_error("filter_img6_kernel: %lld qmask words for %lld queries", (long long)a.qmask_words,
+              (long long)a.nq);
+    return FX_EINVAL;
+  }
+  const void* fn =
+      qm ? (metric == FX_METRIC_COS  ? (const void*)filter_img6_kernel<2, true>
+            : metric == FX_METRIC_IP ? (const void*)filter_img6_kernel<1, true>
+                                     : (const void*)filter_img6_kernel<0, true>)
+         : (metric == FX_METRIC_COS  ? (const void*)filter_img6_kernel<2>
+            : metric == FX_METRIC_IP ? (const void*)filter_img6_kernel<1>
+                                     : (const void*)filter_img6_kernel<0>);
   if (int rc = allow_lds(fn)) return rc;
   int cus = 0;
   if (int rc = device_cus(&cus)) return rc;
@@ -248,7 +290,7 @@ int launch_img6(const FilterArgs& a, int metric, hipStream_t stream) {
   int64_t bx = cus / (slices < cus ? slices : cus);
   if (bx < 1) bx = 1;
   if (bx > a.num_tiles) bx = a.num_tiles;
-  return launch_query_tiles(fn, "filter_img6_kernel", a, kI6Threads, img6_smem(a.dq), bx, fBQ,
+  return launch_query_tiles(fn, "filter_img6_kernel", a, kI6Threads, img6_smem(a.dq, qm), bx, fBQ,
                             kI8QInfo, stream);
 }
 

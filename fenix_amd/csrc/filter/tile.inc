@@ -499,6 +499,7 @@ static int launch_query_tiles(const void* fn, const char* name, const FilterArgs
     b.cand = a.cand + y0 * bq * (int64_t)a.cap;
     if (a.cand_ub) b.cand_ub = a.cand_ub + y0 * bq * (int64_t)a.cap;
     b.nq = a.nq - y0 * bq;
+    if (a.qmask != nullptr) b.qmask = a.qmask + y0 * bq / 32;
     void* args[] = {(void*)&b};
     hipError_t e = hipLaunchKernel(fn, dim3((unsigned)bx, (unsigned)yn), dim3(threads), args, smem,
                                    stream);

@@ -180,15 +180,19 @@ __device__ __forceinline__ void i8_note_row(float* rinfo, float* rterm, float* r
 // v_pk_fma_f32 and one v_pk_add_f32 per two pairs), appends with i8_bounds
 // all-pass phases of at most this many tiles reserve fixed slots even when
 // the slice shares its segments (i8_epilogue)
+// QMASK (filter_img6_kernel's per-query row masks): rqmask holds fBQ / 32
+// words of query bits per row of the tile; bit l32 of word u of a row says
+// whether query 32 u + l32 of the slice admits it.
 constexpr int64_t kAllPassSlotTiles = 64;
-template <int METRIC>
+template <int METRIC, bool QMASK = false>
 __device__ __forceinline__ void i8_epilogue(const f32x16 (&acc)[kI2QT], const float* rinfo,
                                             const float* rterm, const float* rext,
                                             const uint32_t* rrow, const uint32_t* flags,
                                             const f32x4* qtab, const f32x4* qinf,
                                             const FilterArgs& a, int64_t q0, int wid, int h,
                                             int l32, uint32_t* seg, int diag,
-                                            int segcap = FX_I3_SEG) {
+                                            int segcap = FX_I3_SEG,
+                                            const uint32_t* rqmask = nullptr) {
   const int lr0 = wid * 32 + 4 * h;
   const uint32_t fmask = flags[wid * 2 + h], smask = flags[16 + wid * 2 + h];
   // row groups g of 4 rows outside (their values read once from LDS), query
@@ -230,9 +234,26 @@ __device__ __forceinline__ void i8_epilogue(const f32x16 (&acc)[kI2QT], const fl
   // (all_pass: every live row, whatever the test says: with R' = inf a zero
   // row's 0 * inf is a NaN whose sign decides the bit)
   const uint32_t force = a.all_pass ? ~0u : fmask;
+  // QMASK: bit j of qbits[u] is the admission bit of the lane's row j for its
+  // query of tile u (every lane of a half reads the same words: a broadcast);
+  // applied after force, so a forced row and an all-pass phase obey the mask
+  uint32_t qbits[kI2QT];
+#pragma unroll
+  for (int u = 0; u < kI2QT; ++u) qbits[u] = 0xffffu;
+  if constexpr (QMASK) {
+    typedef uint32_t qw_t __attribute__((ext_vector_type(kI2QT)));
+#pragma unroll
+    for (int u = 0; u < kI2QT; ++u) qbits[u] = 0u;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const qw_t w = reinterpret_cast<const qw_t*>(rqmask)[lr0 + (j & 3) + 8 * (j >> 2)];
+#pragma unroll
+      for (int u = 0; u < kI2QT; ++u) qbits[u] |= ((w[u] >> l32) & 1u) << j;
+    }
+  }
 #pragma unroll
   for (int u = 0; u < kI2QT; ++u) {
-    pm[u] = (diag & 1) ? 0u : (~fail[u] | force) & ~smask & 0xffffu;
+    pm[u] = (diag & 1) ? 0u : (~fail[u] | force) & ~smask & qbits[u] & 0xffffu;
     if (q0 + u * 32 + l32 >= a.nq) pm[u] = 0u;
   }
   if (a.all_pass && (segcap <= FX_I3_SEG || a.num_tiles <= kAllPassSlotTiles)) {

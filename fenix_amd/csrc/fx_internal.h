@@ -34,6 +34,10 @@ constexpr int kSelectMaxK = 2048;
 //                        in the workspace for fx_knn_filter_state (test switch; no reduce follows)
 //   qu8_batch_min_work   quint8 batches go through an int8 image from nq * n * d code bytes on
 //                        (use_batched: below it a few exact scans beat the filter's fixed cost)
+//   qmask_batch_min_ratio  in hundredths: concurrent filtered searches run as one per-query-mask
+//                        batch when one by one they would read at least this many times the
+//                        batch's bytes (host policy: engine.qmask_batch_pays; 1.23: the smallest
+//                        measured ratio from which the batch won, profiles/qmask_batch_sweep.json)
 #define FX_OPTIONS(FX_OPTION)                               \
   FX_OPTION(kOptBatched, "batched", 1)                      \
   FX_OPTION(kOptBatchMinQ, "batch_min_queries", 2)          \
@@ -53,7 +57,8 @@ constexpr int kSelectMaxK = 2048;
   FX_OPTION(kOptSelectPrune, "select_prune", 1)             \
   FX_OPTION(kOptScanStream, "scan_stream", -1)             \
   FX_OPTION(kOptFilterHold, "filter_hold", 0)               \
-  FX_OPTION(kOptQu8BatchMinWork, "qu8_batch_min_work", 204800000)
+  FX_OPTION(kOptQu8BatchMinWork, "qu8_batch_min_work", 204800000) \
+  FX_OPTION(kOptQmaskBatchMinRatio, "qmask_batch_min_ratio", 123)
 enum Option : int {
 #define FX_OPTION_ENUM(id, name, dflt) id,
   FX_OPTIONS(FX_OPTION_ENUM)
@@ -98,6 +103,10 @@ struct ScanArgs {
   // block steps of 16U rows dealt round-robin over the grid.  Bit 1: no
   // software pipeline (one tile per wave in flight).  Set by launch_scan.
   int interleave;
+  // Per-query masks: query qi reads the bitmap mask + qi * mask_qstride (words,
+  // < 2^27 for 2^32 rows); 0: one bitmap shared by every query.  (In the
+  // padding before the next pointer: no other field moves.)
+  int mask_qstride;
   // Device-side gate (the batched path's overflow fallback): when non-null, a
   // workgroup of query qi returns at once unless gate[qi * kCountStride] >
   // gate_cap (gate_cap < 0: every query runs).
@@ -283,8 +292,20 @@ struct FilterArgs {
   int diag;               // FX_FILTER_DIAG (diagnostic builds only): 1 no appends, 2 no epilogue,
                           // 4 no MFMA, 8 no query loads, 16 no LDS stores,
                           // 32 no append atomics, 64 no append stores
+  const uint32_t* qmask;  // per-query row masks (fx_qmask_pack: [n][qmask_words], bit q & 31
+                          // of word q >> 5 of CORPUS row r: query q admits r) or null;
+                          // int8 images through filter_img6_kernel<., true> only
+  int64_t qmask_words;    // words per row of qmask (fx_qmask_words(nq))
 };
 int launch_filter(const FilterArgs& a, int metric, hipStream_t stream);
+// which resident-slice build serves a batch with per-query row masks
+// (FilterArgs::qmask): 64 (q64i: nq <= 64, or slices of 64 where a q128 slice
+// does not fit the row length), 128 (q128 slices), 0: neither fits
+int filter_qmask_kind(int dq, int64_t nq);
+// fx_qmask_pack (knn_qmask.hip): nq row bitmaps -> the bit matrix [n][qw]
+int64_t qmask_words(int64_t nq);
+int launch_qmask_pack(const uint32_t* masks, int64_t mask_stride, int64_t nq, int64_t n,
+                      uint32_t* out, hipStream_t stream);
 // the LDS-DMA ring variant (filter/ring.inc ring_kernel) with FX_FILTER_RING=1
 // (the register-staged kernel, filter/staged.inc, otherwise)
 bool filter_ring();

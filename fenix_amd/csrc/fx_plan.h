@@ -24,6 +24,7 @@ struct BatchLayout {
   int64_t cap = 0, tiles = 0, nq_pad = 0;
   int nphases = 0;
   bool img8 = false;    // planned for an int8 filter image (filter_phases_i8)
+  bool qmask = false;   // planned for per-query row masks (filter_img6_kernel<., true>)
   int dq = 0;
   int prune_lists = 0;  // img8: k-lists of the selects' prune pass (select_prune_lists), 0 = none
   int64_t start[16], stride[16], num[16];
@@ -83,8 +84,31 @@ int plan_exact(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, int metri
 // (use_batched), plan_exact otherwise.  img8: the call supplies an int8
 // filter image (single queries may take the batched path); a scan and its
 // reduce must plan with the same flag.
+// qmask: the search brings per-query row masks (fx_knn_search_qmask_ex): an
+// int8-image plan whose filter passes run the resident-slice kernel's QMASK
+// build, or, where that does not apply (no image, k above "i8_max_k", rows not
+// of whole 16-B image pieces, a single query, a row length neither slice
+// build fits: filter_qmask_kind), the exact plan, whose scans read each
+// query's own bitmap.
 int plan_search(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, int metric, bool aligned,
-                bool img8, SearchLayout* s);
+                bool img8, SearchLayout* s, bool qmask = false);
+
+// The row masks of a search: one bitmap shared by every query (or none), or
+// per-query bitmaps mask + q * qstride together with their packed bit matrix
+// (fx_qmask_pack) for the filter.
+struct RowMasks {
+  const uint32_t* mask = nullptr;
+  int64_t qstride = 0;              // words between queries' bitmaps; 0: one shared bitmap
+  const uint32_t* qmask = nullptr;  // [n][qwords], per-query masks only
+  int64_t qwords = 0;
+  RowMasks() = default;
+  RowMasks(const uint32_t* shared) : mask(shared) {}
+  RowMasks from_query(int64_t q0) const {
+    RowMasks m = *this;
+    if (m.mask != nullptr) m.mask += q0 * qstride;
+    return m;
+  }
+};
 
 // the corpus of an entry point that takes it as plain arguments (f32 / f16)
 inline fx_corpus corpus_of(const void* data, int dtype, int64_t n, int64_t d, int64_t row_base) {
@@ -95,9 +119,10 @@ inline fx_corpus corpus_of(const void* data, int dtype, int64_t n, int64_t d, in
 // list, or the corpus's own when rows is null.  Query, outputs, gate and list
 // placement are the caller's.
 ScanArgs scan_args(const ScanPlan& p, const fx_corpus& c, const int32_t* rows, int64_t nrows,
-                   const uint32_t* mask, int64_t k, int mode);
+                   const RowMasks& mask, int64_t k, int mode);
 // launch_scan over any number of queries: a grid holds at most 65 535 of
-// them, so a.q, a.out_lists and a.out_dist (query 0's) advance per chunk
+// them, so a.q, a.out_lists, a.out_dist and per-query masks (query 0's)
+// advance per chunk
 int launch_scan_queries(const ScanPlan& p, ScanArgs a, int64_t nq, hipStream_t st);
 
 }  // namespace fx

@@ -52,7 +52,8 @@
 // kernels themselves are in filter/*.inc, one file per kernel family, and are
 // compiled into five variant translation units (knn_filter_q256.hip, _h256,
 // _q128, _q64, _q64i: one tile shape and namespace each; the header of each
-// says which kernels it holds and which batches come to it).
+// says which kernels it holds and which batches come to it).  The packed
+// per-query row masks the QMASK builds read are made in knn_qmask.hip.
 #include "fx_internal.h"
 
 namespace fx {
@@ -66,11 +67,13 @@ namespace q128 {
 int launch(const FilterArgs& a, int metric, hipStream_t stream);  // knn_filter_q128.hip
 int launch_img6(const FilterArgs& a, int metric, hipStream_t stream);
 bool img6_fits(int dq);
+bool img6_fits_qmask(int dq);
 }
 namespace q64i {  // knn_filter_q64i.hip
 int launch(const FilterArgs& a, int metric, hipStream_t stream);
 int launch_img6(const FilterArgs& a, int metric, hipStream_t stream);
 bool img6_fits(int dq);
+bool img6_fits_qmask(int dq);
 }
 namespace h256 {
 int launch(const FilterArgs& a, int metric, hipStream_t stream);  // knn_filter_h256.hip
@@ -94,6 +97,17 @@ int launch_filter(const FilterArgs& a, int metric, hipStream_t stream) {
   // queries 1.81 vs 1.93 ms), larger ones filter_img3_kernel with 256-query
   // tiles (256 cosine queries: 2.97 ms against 3.34 ms for two img6 slices;
   // option 2 forces the slices, 0 disables img6)
+  // per-query row masks: always the resident-slice kernel's QMASK build, the
+  // only one that tests an admission bit per pair (plan_search planned the
+  // filter only where filter_qmask_kind found a build that fits)
+  if (a.qmask != nullptr) {
+    const int kind = a.img8 ? filter_qmask_kind(a.dq, a.nq) : 0;
+    if (kind == 0) {
+      set_error("filter: per-query masks need an int8 image whose query slice fits (dq=%d)", a.dq);
+      return FX_EUNSUPPORTED;
+    }
+    return kind == 128 ? q128::launch_img6(a, metric, stream) : q64i::launch_img6(a, metric, stream);
+  }
   if (a.img8) {
     const int64_t i6 = option(kOptImg6);
     if (a.nq <= 64) {
@@ -114,6 +128,11 @@ int launch_filter(const FilterArgs& a, int metric, hipStream_t stream) {
   if (a.rowinfo != nullptr && image_tiled()) return q256::launch(a, metric, stream);
   if (a.dtype == FX_DTYPE_F16 && !filter_ring()) return h256::launch(a, metric, stream);
   return q256::launch(a, metric, stream);
+}
+
+int filter_qmask_kind(int dq, int64_t nq) {
+  if (nq > 64 && q128::img6_fits_qmask(dq)) return 128;
+  return q64i::img6_fits_qmask(dq) ? 64 : 0;
 }
 
 // rows per tile of the kernel launch_filter picks for the dtype (every variant

@@ -3,12 +3,14 @@
 // 256-query tile would half pad.  Holds
 //   filter_kernel<float / _Float16, ., false>   both row types (filter/staged.inc)
 //   filter_img3_kernel<., false / true>         tiled fp16 / int8 images (filter/img3.inc)
-//   filter_img6_kernel<.>                       int8 images, a resident slice (filter/img6.inc)
+//   filter_img6_kernel<., false / true>         int8 images, a resident slice (filter/img6.inc);
+//                                               true: per-query row masks (FilterArgs::qmask)
 // and in diagnostic builds filter_kernel<_Float16, ., true> (row-major fp16
 // images) and ring_kernel (filter/ring.inc).  launch_filter (knn_filter.hip)
 // sends launch() every batch of 65..128 queries, and launch_img6() the int8
 // images of such a batch whose slice fits (img6_fits; with option img6 = 2
-// those of larger batches too).
+// those of larger batches too), and every batch of more than 64 queries with
+// per-query row masks whose slice fits (img6_fits_qmask), as slices of 128.
 #include "fx_internal.h"
 
 #include <type_traits>

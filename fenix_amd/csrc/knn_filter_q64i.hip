@@ -3,11 +3,14 @@
 // <= 64 queries, which a 256-query tile would multiply mostly as padding.
 // Holds
 //   filter_img3_kernel<., false / true>   tiled fp16 / int8 images (filter/img3.inc)
-//   filter_img6_kernel<.>                 int8 images, a resident slice (filter/img6.inc)
+//   filter_img6_kernel<., false / true>   int8 images, a resident slice (filter/img6.inc);
+//                                         true: per-query row masks (FilterArgs::qmask)
 // and in diagnostic builds ring_kernel (filter/ring.inc); no register-staged
 // kernel (fp16 and f32 rows of <= 64 queries take the q64 variant).
 // launch_filter (knn_filter.hip) sends it the int8 images of batches of <= 64
-// queries: launch_img6() when the slice fits (img6_fits), else launch().
+// queries: launch_img6() when the slice fits (img6_fits), else launch(); with
+// per-query row masks also larger batches, as slices of 64, where a 128-query
+// slice does not fit the row length (filter_qmask_kind).
 #include "fx_internal.h"
 
 #include <type_traits>

@@ -307,8 +307,14 @@ static int plan_fallback(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k,
 }
 
 int plan_search(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, int metric, bool aligned,
-                bool img8, SearchLayout* s) {
+                bool img8, SearchLayout* s, bool qmask) {
   if (k > kMaxK || !use_batched(nq, dtype, d, aligned, n, img8, k))
+    return plan_exact(n, d, dtype, nq, k, metric, aligned, s);
+  // per-query masks: only the int8 image's resident-slice kernel tests an
+  // admission bit per pair; everything else scans exactly with each query's
+  // own bitmap
+  if (qmask && (!img8 || nq < 2 || k > i8_max_k() || d % 8 != 0 ||
+                filter_qmask_kind(filter_dq((int)d), nq) == 0))
     return plan_exact(n, d, dtype, nq, k, metric, aligned, s);
   // the single-query plan over fb_queries queries serves overflowing queries
   int64_t fq = 1;
@@ -319,6 +325,7 @@ int plan_search(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, int metr
                     img8 && k <= i8_max_k() && d % 8 == 0, &s->batch);
   if (rc) return rc;
   s->batched = true;
+  s->batch.qmask = qmask;
   s->fb_queries = fq;
   s->single_off = s->batch.total;
   s->total = s->batch.total + single_total;
@@ -327,13 +334,14 @@ int plan_search(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, int metr
 
 // ------------------------------------------------------------- exact scan --
 ScanArgs scan_args(const ScanPlan& p, const fx_corpus& c, const int32_t* rows, int64_t nrows,
-                   const uint32_t* mask, int64_t k, int mode) {
+                   const RowMasks& mask, int64_t k, int mode) {
   ScanArgs a = {};
   a.X = c.data;
   a.n = rows != nullptr ? nrows : c.n;
   a.d = (int)c.d;
   a.row_base = c.row_base;
-  a.mask = mask;
+  a.mask = mask.mask;
+  a.mask_qstride = mask.mask != nullptr ? (int)mask.qstride : 0;
   a.rows = rows;
   a.rows_per_block = p.rows_per_block;
   a.k = (int)k;
@@ -353,6 +361,7 @@ int launch_scan_queries(const ScanPlan& p, ScanArgs a, int64_t nq, hipStream_t s
     int rc = launch_scan(p, a, qn, st);
     if (rc) return rc;
     a.q += (size_t)qn * a.d;
+    if (a.mask != nullptr) a.mask += qn * (int64_t)a.mask_qstride;
     if (a.out_lists != nullptr) a.out_lists += (size_t)qn * lists;
     if (a.out_dist != nullptr) a.out_dist += (size_t)qn * a.n;
   }

@@ -263,6 +263,7 @@ struct ScanCtx {
   float qnorm;
   float qscale, qshift;  // uint8 codes: dequantised in registers
   bool topk;
+  const uint32_t* mask;  // scan_kernel: the workgroup's query's bitmap or null (set there)
 };
 
 // row u of the lane group's tile at row `it` of a plain scan (the rings;
@@ -288,8 +289,8 @@ __device__ __forceinline__ void tile_load(RowTile<T, W, L, U>& tile, int64_t it,
     t.valid[u] = t.row[u] < c.hi;
     t.src[u] = t.row[u];
     if (a.rows != nullptr && t.valid[u]) t.src[u] = a.rows[t.row[u]];
-    if (a.mask != nullptr && t.valid[u])
-      t.valid[u] = (a.mask[t.src[u] >> 5] >> (t.src[u] & 31)) & 1u;
+    if (c.mask != nullptr && t.valid[u])
+      t.valid[u] = (c.mask[t.src[u] >> 5] >> (t.src[u] & 31)) & 1u;
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -742,6 +743,10 @@ __global__ void __launch_bounds__(256, kMinWaves<T>) scan_kernel(ScanArgs a) {
   const int nch = (S + CH - 1) / CH;
   ScanCtx c;
   if (!scan_begin<T, W, METRIC>(a, smem, nch * CH * W, c)) return;
+  // per-query bitmaps (ScanArgs::mask_qstride): this workgroup's query's,
+  // offset once.  Here and not in scan_begin: the ring kernels never read a
+  // mask, and their code stays as it was.
+  c.mask = a.mask != nullptr ? a.mask + (int64_t)c.qi * a.mask_qstride : nullptr;
   int64_t lo, gstep;
   scan_partition<U>(a, c, lo, gstep);
 

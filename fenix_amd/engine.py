@@ -192,6 +192,10 @@ class ScanState:
     image: Optional[torch.Tensor]
     rowinfo: Optional[torch.Tensor]
     bits: int
+    # a scan with per-query row masks: the bitmaps [nq, words] and their
+    # packed bit matrix (None: the scan planned no filter), held for the reduce
+    qmasks: Optional[torch.Tensor] = None
+    packed: Optional[torch.Tensor] = None
 
 
 @dataclass
@@ -419,6 +423,8 @@ class Engine:
         # fp16 filter images of f32 corpora, by id of the corpus tensor:
         # (signature, image, rowinfo); dropped when the tensor is collected
         self._images: Dict[int, tuple] = {}
+        # searches that went through the per-query-mask entry point (tests, tools)
+        self.qmask_searches = 0
 
     @classmethod
     def get(cls, device: Optional[torch.device] = None) -> "Engine":
@@ -443,7 +449,8 @@ class Engine:
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def filter_image(self, shard: Shard, nq: int, k: int, metric: int, build: bool = True
+    def filter_image(self, shard: Shard, nq: int, k: int, metric: int, build: bool = True,
+                     qmask: bool = False
                      ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], int]:
         """The filter image of an f32 (or, int8 images, f16 or quint8) shard for a
         search that runs the batched
@@ -469,9 +476,15 @@ class Engine:
         cannot hand its memory to another allocation early."""
         none = (None, None, 0)
         bits = _lib.get_option("filter_image")
+        # (qmask: a search with per-query row masks reads an int8 image or none,
+        # fx_qmask_filter_used)
+        if qmask:
+            used = bits == 8 and _lib.qmask_filter_used(shard.n, shard.d, shard.dtype_id, nq, k,
+                                                        metric) != 0
+        else:
+            used = _lib.filter_image_used(shard.n, shard.d, shard.dtype_id, nq, k, metric)
         # int8 images serve f32, f16 and quint8 corpora, fp16 images f32 ones
-        if ((shard.dtype_id != _lib.DTYPE_F32 and bits != 8) or bits not in (8, 16)
-                or not _lib.filter_image_used(shard.n, shard.d, shard.dtype_id, nq, k, metric)):
+        if (shard.dtype_id != _lib.DTYPE_F32 and bits != 8) or bits not in (8, 16) or not used:
             return none
         t = shard.data
         # an unaligned corpus takes the scan's scalar-load variant, never the
@@ -570,6 +583,52 @@ class Engine:
             )
         )
 
+    def _qmask_tensors(self, shard: Shard, qmasks: torch.Tensor, shared: Optional[torch.Tensor],
+                       packed: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """The per-query bitmaps [nq, words] as the library reads them (32-bit
+        words, contiguous, the shared ``mask`` ANDed in) and, when ``packed``,
+        their bit matrix [n, fx_qmask_words(nq)] (fx_qmask_pack); caller holds lock."""
+        words = (shard.n + 31) // 32
+        qm = qmasks
+        if qm.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+            raise TypeError("qmasks must hold 32-bit words")
+        qm = qm.view(torch.int32).to(self.device).contiguous()
+        if qm.dim() != 2 or qm.shape[1] < words:
+            raise ValueError(f"qmasks must be [nq, >= {words}] words, got {tuple(qm.shape)}")
+        if shared is not None:
+            sw = shared.view(torch.int32)[:words]
+            qm = qm.clone() if qm.data_ptr() == qmasks.data_ptr() else qm
+            qm[:, :words] &= sw.unsqueeze(0)
+        pk = None
+        if packed:
+            nq = qm.shape[0]
+            pk = torch.empty((shard.n, _lib.qmask_words(nq)), dtype=torch.int32,
+                             device=self.device)
+            _lib.check(_lib.load().fx_qmask_pack(_ptr(qm), qm.shape[1], nq, shard.n, _ptr(pk),
+                                                 self._stream()))
+        return qm, pk
+
+    def search_qmask(self, shard: Shard, queries: torch.Tensor, metric: int, k: int,
+                     qmasks: torch.Tensor, shared: Optional[torch.Tensor],
+                     out_dist: torch.Tensor, out_row: torch.Tensor) -> None:
+        """fx_knn_search_qmask_ex on one shard: query i searches the rows its own
+        bitmap ``qmasks[i]`` admits (AND ``shared``), all of them in one pass
+        over the int8 filter image where the library plans the filter; caller
+        holds lock."""
+        nq = queries.shape[0]
+        if qmasks.shape[0] != nq:
+            raise ValueError(f"qmasks holds {qmasks.shape[0]} bitmaps for {nq} queries")
+        img, info, _ = self.filter_image(shard, nq, k, metric, qmask=True)
+        qm, pk = self._qmask_tensors(shard, qmasks, shared, img is not None)
+        c = shard.corpus()
+        ws = self._workspace(_lib.knn_workspace_bytes(shard.n, shard.d, shard.dtype_id, nq, k))
+        self._hold(shard.data, qm, pk)
+        _lib.check(_lib.load().fx_knn_search_qmask_ex(
+            ctypes.byref(c), _ptr(img), _ptr(info), _ptr(queries), nq, metric, k, _ptr(qm),
+            qm.shape[1], _ptr(pk), _ptr(ws), ws.numel(), _ptr(out_dist), _ptr(out_row),
+            self._stream()))
+        self.qmask_searches += 1
+
     def _search_ex(self, shard: Shard, rows: Optional[torch.Tensor], nrows: int,
                    queries: torch.Tensor, metric: int, k: int, mask: Optional[torch.Tensor],
                    out_dist: torch.Tensor, out_row: torch.Tensor) -> None:
@@ -593,13 +652,25 @@ class Engine:
                 t.record_stream(cur)
 
     def scan(self, shard: Shard, queries: torch.Tensor, metric: int, k: int,
-             mask: Optional[torch.Tensor] = None) -> "ScanState":
+             mask: Optional[torch.Tensor] = None,
+             qmasks: Optional[torch.Tensor] = None) -> "ScanState":
         """Phase 1 of search_shard (fx_knn_scan / fx_knn_scan_img8): returns the
         state ``reduce`` completes — the workspace and the exact filter image
         (and its width) the scan planned with, held until the reduce, so the
         pair never plans differently (an image evicted or rebuilt in between
         would make fx_knn_reduce read a filter workspace as scan lists)."""
         nq = queries.shape[0]
+        if qmasks is not None:  # per-query row masks (``mask`` ANDed in): fx_knn_scan_qmask_ex
+            img, info, bits = self.filter_image(shard, nq, k, metric, qmask=True)
+            qm, pk = self._qmask_tensors(shard, qmasks, mask, img is not None)
+            c = shard.corpus()
+            ws = self._workspace(_lib.knn_workspace_bytes(shard.n, shard.d, shard.dtype_id, nq, k))
+            self._hold(shard.data, qm, pk)
+            _lib.check(_lib.load().fx_knn_scan_qmask_ex(
+                ctypes.byref(c), _ptr(img), _ptr(info), _ptr(queries), nq, metric, k, _ptr(qm),
+                qm.shape[1], _ptr(pk), _ptr(ws), ws.numel(), self._stream()))
+            self.qmask_searches += 1
+            return ScanState(ws, img, info, bits, qm, pk)
         img, info, bits = self.filter_image(shard, nq, k, metric)
         ws = self._workspace(_lib.knn_workspace_bytes(shard.n, shard.d, shard.dtype_id, nq, k,
                                                       img8=bits == 8))
@@ -630,6 +701,13 @@ class Engine:
         nq = queries.shape[0]
         ws = state.ws
         L = _lib.load()
+        if state.qmasks is not None:  # (the scan's own bitmaps, its mask already ANDed in)
+            c = shard.corpus()
+            _lib.check(L.fx_knn_reduce_qmask_ex(
+                ctypes.byref(c), _ptr(state.image), _ptr(queries), nq, metric, k,
+                _ptr(state.qmasks), state.qmasks.shape[1], _ptr(state.packed), _ptr(ws),
+                ws.numel(), _ptr(out_dist), _ptr(out_row), self._stream()))
+            return
         if shard.dtype_id == _lib.DTYPE_QU8:
             c = shard.corpus()
             _lib.check(L.fx_knn_reduce_img8_ex(
@@ -655,6 +733,8 @@ class Engine:
         """fx_knn_filter_counts after ``scan``: each query's final candidate
         count (> cap: the exact scan recomputed it) and the capacity; (None,
         -1) when the scan did not run the filter.  Synchronises (tests, tools)."""
+        if state.qmasks is not None and state.image is None:
+            return None, -1  # (per-query masks without an image: exact scans)
         out = torch.zeros(nq, dtype=torch.int32, device=self.device)
         cap = ctypes.c_int64(0)
         _lib.check(_lib.load().fx_knn_filter_counts(
@@ -683,7 +763,8 @@ class Engine:
         return tuple(t.cpu().numpy().view(np.uint64) for t in (thr, cand, cub))
 
     def filter_bounds(self, shard: Shard, queries: torch.Tensor, metric: int, k: int,
-                      mask: Optional[torch.Tensor] = None) -> Optional[dict]:
+                      mask: Optional[torch.Tensor] = None,
+                      qmasks: Optional[torch.Tensor] = None) -> Optional[dict]:
         """The batched filter's own output for one search: ``scan`` under the
         option "filter_hold" (the phases stop after their last filter pass; no
         ``reduce`` follows), read back to the host.  Per query q, over slots
@@ -695,7 +776,7 @@ class Engine:
         search does not run the filter.  Synchronises (tests, tools)."""
         nq = queries.shape[0]
         with _lib.options(filter_hold=1):
-            st = self.scan(shard, queries, metric, k, mask)
+            st = self.scan(shard, queries, metric, k, mask, qmasks)
             counts, cap = self.filter_counts(shard, nq, metric, k, st)
             if counts is None:
                 return None
@@ -752,7 +833,10 @@ class Engine:
 
     def _search_one(self, shard: Shard, queries: torch.Tensor, metric: int, k: int,
                     mask: Optional[torch.Tensor], count: Optional[int], out_dist: torch.Tensor,
-                    out_row: torch.Tensor) -> None:
+                    out_row: torch.Tensor, qmasks: Optional[torch.Tensor] = None) -> None:
+        if qmasks is not None:  # (count: the per-query kept rows; the library needs none)
+            self.search_qmask(shard, queries, metric, k, qmasks, mask, out_dist, out_row)
+            return
         if mask is not None and count is not None and count < self.SPARSE * shard.n:
             if count == 0:
                 out_dist.fill_(float("nan"))
@@ -803,15 +887,22 @@ class Engine:
                masks: Optional[Sequence[Optional[torch.Tensor]]] = None,
                counts: Optional[Sequence[Optional[int]]] = None,
                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+               qmasks: Optional[Sequence[Optional[torch.Tensor]]] = None,
                ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Exact top-k over several shards (sources): per-shard scan, then merge.
         ``counts`` (optional): rows each mask keeps, to pick the row-list scan.
         ``out`` (one shard only): the (dist [nq, k] f32, row [nq, k] i64)
-        tensors on this device to write into (search_host's packed result)."""
+        tensors on this device to write into (search_host's packed result).
+        ``qmasks`` (optional): per shard a [nq, words] tensor of 32-bit words on
+        this device, query i's own row bitmap of the shard (``masks[i]`` is
+        ANDed into each; ``counts[i]``, then the per-query kept rows, is not
+        needed): every query searches its own rows in one call
+        (fx_knn_search_qmask_ex), results equal to nq masked searches."""
         queries = _to_device(queries, self.device)
         nq = queries.shape[0]
         mask_of = (lambda i: masks[i]) if masks else (lambda i: None)
         count_of = (lambda i: counts[i]) if counts else (lambda i: None)
+        qmask_of = (lambda i: qmasks[i]) if qmasks else (lambda i: None)
         if out is not None and len(shards) != 1:
             raise ValueError("Engine.search: out= needs exactly one shard")
         with self.lock:
@@ -819,9 +910,10 @@ class Engine:
                 od, orow = out if out is not None else (
                     torch.empty((nq, k), dtype=torch.float32, device=self.device),
                     torch.empty((nq, k), dtype=torch.int64, device=self.device))
-                self._search_one(shards[0], queries, metric, k, mask_of(0), count_of(0), od, orow)
+                self._search_one(shards[0], queries, metric, k, mask_of(0), count_of(0), od, orow,
+                                 qmask_of(0))
                 return od, orow
-            if self._one_merge(shards, nq, k, metric, masks):
+            if qmasks is None and self._one_merge(shards, nq, k, metric, masks):
                 od = torch.empty((nq, k), dtype=torch.float32, device=self.device)
                 orow = torch.empty((nq, k), dtype=torch.int64, device=self.device)
                 self._search_shards(shards, queries, metric, k, od, orow)
@@ -831,7 +923,8 @@ class Engine:
             for i, sh in enumerate(shards):
                 td = torch.empty((nq, k), dtype=torch.float32, device=self.device)
                 tr = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-                self._search_one(sh, queries, metric, k, mask_of(i), count_of(i), td, tr)
+                self._search_one(sh, queries, metric, k, mask_of(i), count_of(i), td, tr,
+                                 qmask_of(i))
                 pd[:, i] = td
                 pr[:, i] = tr
             return self.merge(pd, pr, k)
@@ -1065,7 +1158,8 @@ def _to_host(*ts: torch.Tensor) -> Tuple[np.ndarray, ...]:
 
 
 def _search_packed(shard: Shard, queries: torch.Tensor, metric: int, k: int,
-                   masks=None, counts=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                   masks=None, counts=None, qmasks=None
+                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """One shard's search with the k winning rows gathered behind it, all
     three results written into ONE device buffer [rows i64 | dist f32 | pad |
     vectors] and brought back with ONE D2H and one synchronisation (three
@@ -1084,7 +1178,8 @@ def _search_packed(shard: Shard, queries: torch.Tensor, metric: int, k: int,
         orow = packed[:off_d].view(torch.int64).view(nq, k)
         od = packed[off_d:off_d + 4 * m].view(torch.float32).view(nq, k)
         vecs = packed[off_v:].view(shard.data.dtype).view(m, shard.d)
-        Engine.get(dev).search([shard], queries, metric, k, masks, counts, out=(od, orow))
+        Engine.get(dev).search([shard], queries, metric, k, masks, counts, out=(od, orow),
+                               qmasks=qmasks)
         flat = orow.reshape(-1)
         local = (flat.clamp(0, max(shard.n - 1, 0)) if shard.row_base == 0
                  else (flat - shard.row_base).clamp_(0, max(shard.n - 1, 0)))
@@ -1102,6 +1197,54 @@ def _np_dtype(dt: torch.dtype):
     return {torch.float32: np.float32, torch.float16: np.float16, torch.uint8: np.uint8}[dt]
 
 
+def qmask_batch_pays(counts: Sequence[Optional[int]], n: int, d: int, itemsize: int, nq: int,
+                     min_ratio: Optional[float] = None) -> bool:
+    """Whether ``nq`` concurrent searches of an n x d column, request q keeping
+    ``counts[q]`` rows (None: all of them), are worth one per-query-mask pass
+    over the int8 image, by the bytes each way reads:
+
+    * the batch: n (d + 16) image and row-term bytes plus the n x
+      fx_qmask_words(nq) words of admission bits;
+    * one by one: a request keeping less than ``Engine.SPARSE`` of the rows
+      reads its kept rows (the row-list scan), any other walks all n.
+
+    True when the second is at least ``min_ratio`` (default: the library
+    option "qmask_batch_min_ratio", in hundredths) times the first."""
+    if min_ratio is None:
+        min_ratio = _lib.get_option("qmask_batch_min_ratio") / 100.0
+    words = ((nq + 31) // 32 + 3) // 4 * 4
+    batch = n * (d + 16) + n * 4 * words
+    single = 0
+    for c in counts:
+        rows = n if c is None or c >= Engine.SPARSE * n else c
+        single += rows * d * itemsize
+    return single >= min_ratio * batch
+
+
+def _batch_qmasks(shards: Sequence[Shard], extras: Sequence[Optional[tuple]]):
+    """The per-shard [nq, words] bitmaps and per-request kept-row counts of a
+    coalesced batch whose requests carry (masks, counts) payloads (None: a
+    plain request, which admits every row)."""
+    qmasks, totals = [], [0] * len(extras)
+    for i, s in enumerate(shards):
+        dev = s.data.device
+        words = max(1, (s.n + 31) // 32)
+        rows = []
+        with torch.cuda.device(dev):
+            ones = None
+            for j, ex in enumerate(extras):
+                m = ex[0][i] if ex is not None and ex[0] is not None else None
+                c = ex[1][i] if ex is not None and ex[1] is not None else None
+                if m is None:
+                    if ones is None:
+                        ones = torch.full((words,), -1, dtype=torch.int32, device=dev)
+                    m, c = ones, s.n
+                totals[j] += s.n if c is None else int(c)
+                rows.append(m.view(torch.int32)[:words])
+            qmasks.append(torch.stack(rows))
+    return qmasks, totals
+
+
 def search_host(shards: Sequence[Shard], queries: torch.Tensor, metric: int, k: int,
                 masks: Optional[Sequence[Optional[torch.Tensor]]] = None,
                 counts: Optional[Sequence[Optional[int]]] = None, gather: bool = False,
@@ -1112,24 +1255,47 @@ def search_host(shards: Sequence[Shard], queries: torch.Tensor, metric: int, k: 
     With ``gather`` the result rows' stored values are gathered on the
     device behind the search (``gather_rows``) and come back with the
     distances and rows in one synchronisation (None when the shards span
-    devices).  A single unfiltered query goes through the serving coalescer
-    like ``search_all``."""
-    def run(qs: torch.Tensor, kk: int, ms=None, cs=None) -> Tuple[np.ndarray, ...]:
+    devices).  A single query goes through the serving coalescer, with its
+    masks and counts (a filtered or probe search) as the request's payload:
+    concurrent requests over the same shards run as one batch, and a batch
+    in which any request brings masks runs as one per-query-mask search
+    where ``qmask_batch_pays`` says so (every shard served by the int8
+    filter), else request by request exactly as each would run alone."""
+    def run(qs: torch.Tensor, kk: int, ms=None, cs=None, qms=None) -> Tuple[np.ndarray, ...]:
         if gather and len(shards) == 1 and shards[0].n > 0:
-            return _search_packed(shards[0], qs, metric, kk, ms, cs)
-        d, r = _search_all(shards, qs, metric, kk, ms, cs)
+            return _search_packed(shards[0], qs, metric, kk, ms, cs, qms)
+        d, r = _search_all(shards, qs, metric, kk, ms, cs, qms)
         v = gather_rows(shards, r) if gather else None
         if v is None:
             return _to_host(d, r)
         with torch.cuda.device(r.device):
             return _to_host(d, r, v)
 
-    if (queries.shape[0] == 1 and masks is None and counts is None and coalesce.enabled()
-            and k <= _lib.load().fx_max_k()):
+    def run_batch(qs: np.ndarray, kk: int, extras=None) -> Tuple[np.ndarray, ...]:
+        nq = qs.shape[0]
+        if extras is None or all(e is None for e in extras):
+            return run(torch.from_numpy(qs), kk)
+        if nq >= 2 and shards:
+            served = all(s.n > 0 and _lib.get_option("filter_image") == 8 and
+                         _lib.qmask_filter_used(s.n, s.d, s.dtype_id, nq, kk, metric) != 0
+                         for s in shards)
+            if served:
+                qms, totals = _batch_qmasks(shards, extras)
+                if qmask_batch_pays(totals, sum(s.n for s in shards), shards[0].d,
+                                    shards[0].data.element_size(), nq):
+                    return run(torch.from_numpy(qs), kk, None, None, qms)
+        # one by one, each exactly as it would run alone
+        outs = []
+        for i, ex in enumerate(extras):
+            ms, cs = ex if ex is not None else (None, None)
+            outs.append(run(torch.from_numpy(qs[i:i + 1]), kk, ms, cs))
+        return tuple(np.concatenate(p) for p in zip(*outs))
+
+    if queries.shape[0] == 1 and coalesce.enabled() and k <= _lib.load().fx_max_k():
         key = (tuple((id(s.data), s.data.data_ptr(), s.n, s.row_base) for s in shards), metric,
                gather)
-        parts = coalesce.default().search(key, lambda qs, kk: run(torch.from_numpy(qs), kk),
-                                          queries.cpu().numpy(), k)
+        extra = None if masks is None and counts is None else (masks, counts)
+        parts = coalesce.default().search(key, run_batch, queries.cpu().numpy(), k, extra)
     else:
         parts = run(queries, k, masks, counts)
     if len(parts) == 3:
@@ -1172,6 +1338,7 @@ def gather_mode(devs: Sequence[torch.device]) -> str:
 def _search_all(shards: Sequence[Shard], queries: torch.Tensor, metric: int, k: int,
                 masks: Optional[Sequence[Optional[torch.Tensor]]] = None,
                 counts: Optional[Sequence[Optional[int]]] = None,
+                qmasks: Optional[Sequence[Optional[torch.Tensor]]] = None,
                 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Exact top-k over shards that may live on several devices.
 
@@ -1193,7 +1360,9 @@ def _search_all(shards: Sequence[Shard], queries: torch.Tensor, metric: int, k: 
             eng = Engine.get(dev)
             ms = [masks[i] for i in idx] if masks is not None else None
             cs = [counts[i] for i in idx] if counts is not None else None
-            per.append(eng.search([shards[i] for i in idx], queries, metric, k, ms, cs))
+            qs = [qmasks[i] for i in idx] if qmasks is not None else None
+            extra = {"qmasks": qs} if qs is not None else {}
+            per.append(eng.search([shards[i] for i in idx], queries, metric, k, ms, cs, **extra))
     if len(per) == 1:
         return per[0]
     devs = list(groups)

@@ -126,6 +126,12 @@ int fx_device_count(int* out);
  *                            filter pass: fx_knn_filter_state then reads the
  *                            pairs' lower / upper bounds and the threshold that
  *                            pass tested against; no reduce may follow (test switch)
+ *   "qmask_batch_min_ratio" 123  in hundredths: the serving host runs concurrent
+ *                            filtered / probe searches of a column as one
+ *                            per-query-mask batch (fx_knn_search_qmask_ex) when,
+ *                            run one by one, they would read at least this many
+ *                            times the bytes of the batch's one image pass
+ *                            (host policy only; the library does not read it)
  * fx_set_option: FX_EINVAL for an unknown name.  Options are read when a call
  * plans its launches; set them while no search is in flight.
  */
@@ -487,6 +493,58 @@ int fx_knn_search_img8_ex(const fx_corpus* c, const void* image, const float* ro
                           const float* queries, int64_t nq, int metric, int64_t k,
                           const uint32_t* mask, void* ws, size_t ws_bytes, float* out_dist,
                           int64_t* out_row, void* stream);
+
+/*
+ * Per-query row masks: a batch whose every query brings its own row bitmap
+ * (the filtered and probe searches of index.py:113-126, one filter per
+ * client) in ONE pass over the int8 filter image.  The filter tests every
+ * (row, query) pair anyway; fx_qmask_pack supplies the one admission bit per
+ * pair it needs.
+ *   fx_qmask_words(nq): words per row of the packed matrix, ceil(nq / 32)
+ *     rounded up to a multiple of 4 (16-B groups of 128 queries).
+ *   fx_qmask_pack: masks [nq][mask_stride] uint32 (query q's ordinary bitmap,
+ *     bit r & 31 of word r >> 5; mask_stride >= ceil(n / 32)) -> out
+ *     [n][fx_qmask_words(nq)] uint32, 16-B aligned: bit q & 31 of word q >> 5
+ *     of row r is set when query q admits row r; padding bits are zero, bits
+ *     of rows >= n in the last input word are ignored.  Indexed by corpus row.
+ *   fx_knn_scan_qmask_ex / fx_knn_reduce_qmask_ex / fx_knn_search_qmask_ex =
+ *     the *_img8_ex triple with (masks, mask_stride, qmask) in place of mask:
+ *     the bitmaps and their packed matrix (both stay valid until the search
+ *     has run).  image may be NULL.  masks NULL: every query admits every row
+ *     (qmask is then not read).  k <= fx_max_k().
+ * With an image, nq >= 2, k <= option "i8_max_k", rows of whole 16-B image
+ * pieces (d % 8 == 0; quint8: the batch gate of fx_knn_search_img8_ex) and a
+ * row length one of the resident-slice kernels holds, the filter passes run
+ * with the admission bits (slices of 64 queries for nq <= 64, else of 128
+ * where 128 queries of that length fit a workgroup's LDS, else of 64);
+ * queries whose candidates overflow, and every other shape, take the exact
+ * scan with each query's own bitmap.  Rows and distance bits equal nq
+ * fx_knn_search_ex(c, NULL, -1, q_i, 1, ..., masks + i * mask_stride, ...)
+ * calls; a query whose mask keeps fewer than k rows pads with NaN / -1.
+ * Workspace: fx_knn_workspace_bytes_img8.  fx_knn_filter_counts / _state read
+ * a filter-planned scan's state as an img8 scan's.  fx_qmask_filter_used:
+ * *out = 64 or 128 (the slice width) when a search of that shape with
+ * per-query masks runs the filter (option "filter_image" 8), 0 when it scans
+ * exactly.
+ */
+int64_t fx_qmask_words(int64_t nq);
+int fx_qmask_pack(const uint32_t* masks, int64_t mask_stride, int64_t nq, int64_t n,
+                  uint32_t* out, void* stream);
+int fx_qmask_filter_used(int64_t n, int64_t d, int dtype, int64_t nq, int64_t k, int metric,
+                         int* out);
+int fx_knn_scan_qmask_ex(const fx_corpus* c, const void* image, const float* rowinfo,
+                         const float* queries, int64_t nq, int metric, int64_t k,
+                         const uint32_t* masks, int64_t mask_stride, const uint32_t* qmask,
+                         void* ws, size_t ws_bytes, void* stream);
+int fx_knn_reduce_qmask_ex(const fx_corpus* c, const void* image, const float* queries,
+                           int64_t nq, int metric, int64_t k, const uint32_t* masks,
+                           int64_t mask_stride, const uint32_t* qmask, void* ws, size_t ws_bytes,
+                           float* out_dist, int64_t* out_row, void* stream);
+int fx_knn_search_qmask_ex(const fx_corpus* c, const void* image, const float* rowinfo,
+                           const float* queries, int64_t nq, int metric, int64_t k,
+                           const uint32_t* masks, int64_t mask_stride, const uint32_t* qmask,
+                           void* ws, size_t ws_bytes, float* out_dist, int64_t* out_row,
+                           void* stream);
 
 int fx_knn_search_shards_workspace_bytes(const fx_corpus* shards, int nshards, int64_t nq,
                                          int64_t k, size_t* out_bytes);
