@@ -71,6 +71,8 @@ SYMBOLS = (
     "fx_code_assign",
     "fx_kmeans_step_workspace_bytes",
     "fx_kmeans_step",
+    "fx_code_assign_ex",
+    "fx_kmeans_step_ex",
     "fx_code_probe_workspace_bytes",
     "fx_code_probe",
     "fx_code_mask",
@@ -216,6 +218,11 @@ def load() -> ctypes.CDLL:
         L.fx_kmeans_step_workspace_bytes.restype = ci
         L.fx_kmeans_step.argtypes = [vp, ci, i64, i64, i64, vp, i64, ci, vp, sz, vp]
         L.fx_kmeans_step.restype = ci
+        L.fx_code_assign_ex.argtypes = [ctypes.POINTER(Corpus), vp, i64, i64, ci, vp, sz, vp, vp,
+                                        vp, vp]
+        L.fx_code_assign_ex.restype = ci
+        L.fx_kmeans_step_ex.argtypes = [ctypes.POINTER(Corpus), i64, vp, i64, ci, vp, sz, vp]
+        L.fx_kmeans_step_ex.restype = ci
         L.fx_code_probe_workspace_bytes.argtypes = [i64, i64, i64, psz]
         L.fx_code_probe_workspace_bytes.restype = ci
         L.fx_code_probe.argtypes = [vp, i64, i64, i64, i64, vp, sz, vp, vp, vp, vp]

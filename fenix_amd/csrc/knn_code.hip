@@ -11,7 +11,9 @@
 //   assign_kernel    nearest codeword per (row, codebook).  An fp32 MFMA GEMM of
 //                    128-row x 256-codeword tiles (the tiling of the removed
 //                    fp32-MFMA batch kernel, DESIGN.md "Batched queries"; f16
-//                    rows are widened while staging to LDS)
+//                    rows are widened while staging to LDS; quint8 rows are
+//                    prefetched as raw codes and dequantised there,
+//                    scale * (float)(code - zero_point): the f32 bits)
 //                    whose epilogue turns each dot product into the metric's
 //                    distance, min-reduces 64-bit (order_key(dist) << 32 | index)
 //                    keys over each codebook segment in registers and lane
@@ -34,6 +36,8 @@
 #include "fx_wave.h"
 
 namespace fx {
+
+int validate_quant(const fx_corpus& c);  // knn_plan.hip
 
 namespace {
 
@@ -59,7 +63,9 @@ struct AssignArgs {
   const void* X;     // group g reads rows [g*rows, (g+1)*rows) of a [.][d] matrix
   int64_t rows;      // rows per group
   int d;
-  int vec;           // rows 16-B (f32) / 8-B (f16) aligned and d % 4 == 0
+  int vec;           // rows 16-B (f32) / 8-B (f16) / 4-B (quint8) aligned and d % 4 == 0
+  float scale;       // quint8 rows: value = scale * (code - zp), one rounding
+  int zp;
   const float* W;    // padded codewords [groups][slots][d4]
   const float* wn;   // per slot: ||w||^2 (L2), max(||w||, eps) (cosine)
   int d4;            // d rounded up to 4
@@ -71,41 +77,88 @@ struct AssignArgs {
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
+// One staged piece of a row: 4 consecutive components.  float / f16 rows are
+// widened when they are loaded; quint8 rows stay their 4 raw code bytes until
+// cstore (a quarter of the prefetch registers), with the number of leading
+// components that exist beside them: padding is 0.f, not the value of code 0.
 template <typename T>
-__device__ __forceinline__ f32x4 x_piece(const T* X, int64_t gr, int d, int k, int vec) {
-  const T* p = X + gr * (int64_t)d + k;
-  if (vec) {
-    if constexpr (sizeof(T) == 4) {
-      return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-    } else {
-      const u32x2 u = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
-      const f16x4 hv = __builtin_bit_cast(f16x4, u);
-      f32x4 v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (float)hv[e];
-      return v;
-    }
-  }
+struct XPiece {
   f32x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = (k + e < d) ? (float)p[e] : 0.f;
-  return v;
+};
+template <>
+struct XPiece<uint8_t> {
+  uint32_t raw;
+  int nv;
+};
+
+template <typename T>
+__device__ __forceinline__ XPiece<T> x_zero() {
+  if constexpr (sizeof(T) == 1) {
+    return XPiece<T>{0u, 0};
+  } else {
+    return XPiece<T>{f32x4(0.f)};
+  }
 }
 
+template <typename T>
+__device__ __forceinline__ XPiece<T> x_piece(const T* X, int64_t gr, int d, int k, int vec) {
+  const T* p = X + gr * (int64_t)d + k;
+  if constexpr (sizeof(T) == 1) {
+    if (vec) return XPiece<T>{__builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p)), 4};
+    uint32_t raw = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (k + e < d) raw |= (uint32_t)p[e] << (8 * e);
+    return XPiece<T>{raw, d - k < 4 ? d - k : 4};
+  } else {
+    if (vec) {
+      if constexpr (sizeof(T) == 4) {
+        return XPiece<T>{__builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p))};
+      } else {
+        const u32x2 u = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
+        const f16x4 hv = __builtin_bit_cast(f16x4, u);
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (float)hv[e];
+        return XPiece<T>{v};
+      }
+    }
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (k + e < d) ? (float)p[e] : 0.f;
+    return XPiece<T>{v};
+  }
+}
+
+// the f32 components of a piece: scale * (float)(code - zp) for quint8 rows
+template <typename T>
+__device__ __forceinline__ f32x4 x_value(const XPiece<T>& x, float scale, int zp) {
+  if constexpr (sizeof(T) == 1) {
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      v[e] = e < x.nv ? scale * (float)((int)((x.raw >> (8 * e)) & 0xffu) - zp) : 0.f;
+    return v;
+  } else {
+    return x.v;
+  }
+}
+
+template <typename T>
 struct CPrefetch {
-  f32x4 x[kCM * 8 / kCThreads];
+  XPiece<T> x[kCM * 8 / kCThreads];
   f32x4 w[kCQ * 8 / kCThreads];
 };
 
 template <typename T>
-__device__ __forceinline__ void cprefetch(CPrefetch& p, const AssignArgs& a, const T* X,
+__device__ __forceinline__ void cprefetch(CPrefetch<T>& p, const AssignArgs& a, const T* X,
                                           const float* W, int64_t r0, int s0, int k0, int tid) {
 #pragma unroll
   for (int i = 0; i < kCM * 8 / kCThreads; ++i) {
     const int idx = i * kCThreads + tid;  // row = idx/8, col4 = idx%8
     const int64_t gr = r0 + (idx >> 3);
     const int k = k0 + (idx & 7) * 4;
-    p.x[i] = (gr < a.rows && k < a.d) ? x_piece(X, gr, a.d, k, a.vec) : f32x4(0.f);
+    p.x[i] = (gr < a.rows && k < a.d) ? x_piece(X, gr, a.d, k, a.vec) : x_zero<T>();
   }
 #pragma unroll
   for (int i = 0; i < kCQ * 8 / kCThreads; ++i) {
@@ -116,11 +169,14 @@ __device__ __forceinline__ void cprefetch(CPrefetch& p, const AssignArgs& a, con
   }
 }
 
-__device__ __forceinline__ void cstore(const CPrefetch& p, AssignShared* sh, int buf, int tid) {
+template <typename T>
+__device__ __forceinline__ void cstore(const CPrefetch<T>& p, const AssignArgs& a,
+                                       AssignShared* sh, int buf, int tid) {
 #pragma unroll
   for (int i = 0; i < kCM * 8 / kCThreads; ++i) {
     const int idx = i * kCThreads + tid;
-    *reinterpret_cast<f32x4*>(&sh->xs[buf][(idx >> 3) * kCLds + (idx & 7) * 4]) = p.x[i];
+    *reinterpret_cast<f32x4*>(&sh->xs[buf][(idx >> 3) * kCLds + (idx & 7) * 4]) =
+        x_value<T>(p.x[i], a.scale, a.zp);
   }
 #pragma unroll
   for (int i = 0; i < kCQ * 8 / kCThreads; ++i) {
@@ -172,10 +228,10 @@ __global__ void __launch_bounds__(kCThreads, 1) assign_kernel(AssignArgs a) {
     for (int qt = 0; qt < kCTiles; ++qt) acc[qt] = f32x16(0.f);
     float sumsq = 0.f;
 
-    CPrefetch pf;
+    CPrefetch<T> pf;
     cprefetch<T>(pf, a, X, W, r0, s0, 0, tid);
     __syncthreads();  // the previous tile's epilogue is done with the LDS
-    cstore(pf, sh, 0, tid);
+    cstore<T>(pf, a, sh, 0, tid);
     __syncthreads();
     for (int c = 0; c < nchunks; ++c) {
       const int buf = c & 1;
@@ -197,7 +253,7 @@ __global__ void __launch_bounds__(kCThreads, 1) assign_kernel(AssignArgs a) {
             acc[qt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bv[t], acc[qt], 0, 0, 0);
         }
       }
-      if (c + 1 < nchunks) cstore(pf, sh, buf ^ 1, tid);
+      if (c + 1 < nchunks) cstore<T>(pf, a, sh, buf ^ 1, tid);
       __syncthreads();
     }
 
@@ -303,17 +359,28 @@ __global__ void finalize_kernel(const uint64_t* __restrict__ keys, int64_t n, in
   if (out_code) out_code[row] = code;
 }
 
+// a stored component as f32: quint8 codes are dequantised on read, exactly as
+// the assign kernel stages them (scale * (float)(code - zp), one rounding)
+template <typename T>
+__device__ __forceinline__ float row_value(T v, float scale, int zp) {
+  if constexpr (sizeof(T) == 1) {
+    return scale * (float)((int)v - zp);
+  } else {
+    return (float)v;
+  }
+}
+
 // one wave per row: mode 0 -> sum of squares, mode 1 -> max(||x||, eps)
 template <typename T>
 __global__ void rownorm_kernel(const T* __restrict__ X, int64_t n, int d, int mode,
-                               float* __restrict__ out) {
+                               float* __restrict__ out, float scale, int zp) {
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= n) return;
   const T* p = X + row * (int64_t)d;
   float s = 0.f;
   for (int i = lane; i < d; i += 64) {
-    const float v = (float)p[i];
+    const float v = row_value(p[i], scale, zp);
     s = fmaf(v, v, s);
   }
 #pragma unroll
@@ -350,7 +417,7 @@ __global__ void __launch_bounds__(kUpdThreads) update_kernel(const T* __restrict
                                                              const int32_t* __restrict__ assign,
                                                              const float* __restrict__ rnorm,
                                                              float* __restrict__ W, int ks,
-                                                             int cosine) {
+                                                             int cosine, float scale, int zp) {
   __shared__ int list[kUpdThreads];
   __shared__ int wcount[16];
   __shared__ float red[16];
@@ -399,7 +466,7 @@ __global__ void __launch_bounds__(kUpdThreads) update_kernel(const T* __restrict
         if (dim < d) {
           float v[4];
 #pragma unroll
-          for (int t = 0; t < 4; ++t) v[t] = (float)xr[t][dim];
+          for (int t = 0; t < 4; ++t) v[t] = row_value(xr[t][dim], scale, zp);
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
             if (e0 + t < total) acc[u] += cosine ? v[t] / sc[t] : v[t];
@@ -624,9 +691,20 @@ void* assign_fn() {
   return (void*)assign_kernel<T, METRIC>;
 }
 
-int run_assign(const void* X, int dtype, int64_t groups, int64_t rows, int64_t d,
+// the rows of an assign or a k-means step: [.][d] of dtype, with the map of
+// FX_DTYPE_QU8 codes (value = scale * (code - zp); 1, 0 otherwise)
+struct RowSrc {
+  const void* x;
+  int dtype;
+  float scale;
+  int zp;
+};
+
+int run_assign(const RowSrc& src, int64_t groups, int64_t rows, int64_t d,
                const float* cw, int64_t nbg, int64_t ks, int metric, char* ws,
                const AssignLayout& l, hipStream_t st) {
+  const void* X = src.x;
+  const int dtype = src.dtype;
   float* W = reinterpret_cast<float*>(ws + l.off_w);
   float* wn = reinterpret_cast<float*>(ws + l.off_wn);
   uint64_t* keys = reinterpret_cast<uint64_t*>(ws + l.off_keys);
@@ -645,8 +723,10 @@ int run_assign(const void* X, int dtype, int64_t groups, int64_t rows, int64_t d
   a.X = X;
   a.rows = rows;
   a.d = (int)d;
-  const size_t esz = dtype == FX_DTYPE_F32 ? 4 : 2;
+  const size_t esz = dtype == FX_DTYPE_F32 ? 4 : dtype == FX_DTYPE_F16 ? 2 : 1;
   a.vec = (d % 4 == 0) && ((uintptr_t)X % (4 * esz) == 0);
+  a.scale = src.scale;
+  a.zp = src.zp;
   a.W = W;
   a.wn = wn;
   a.d4 = l.d4;
@@ -660,9 +740,12 @@ int run_assign(const void* X, int dtype, int64_t groups, int64_t rows, int64_t d
   if (dtype == FX_DTYPE_F32) {
     fn = metric == FX_METRIC_L2 ? assign_fn<float, 0>()
          : metric == FX_METRIC_IP ? assign_fn<float, 1>() : assign_fn<float, 2>();
-  } else {
+  } else if (dtype == FX_DTYPE_F16) {
     fn = metric == FX_METRIC_L2 ? assign_fn<_Float16, 0>()
          : metric == FX_METRIC_IP ? assign_fn<_Float16, 1>() : assign_fn<_Float16, 2>();
+  } else {
+    fn = metric == FX_METRIC_L2 ? assign_fn<uint8_t, 0>()
+         : metric == FX_METRIC_IP ? assign_fn<uint8_t, 1>() : assign_fn<uint8_t, 2>();
   }
   const size_t smem = sizeof(AssignShared);
   if (int rc2 = allow_lds((const void*)fn)) return rc2;
@@ -686,12 +769,14 @@ int run_assign(const void* X, int dtype, int64_t groups, int64_t rows, int64_t d
   return check_launch("assign_kernel");
 }
 
-int validate_code(int64_t n, int64_t d, int dtype, int64_t nb, int64_t ks, int metric) {
+// qu8: the caller carries the codes' map (the _ex entry points)
+int validate_code(int64_t n, int64_t d, int dtype, int64_t nb, int64_t ks, int metric,
+                  bool qu8 = false) {
   if (n < 0 || d <= 0 || d > (1 << 20)) {
     set_error("invalid shape n=%lld d=%lld", (long long)n, (long long)d);
     return FX_EINVAL;
   }
-  if (dtype != FX_DTYPE_F32 && dtype != FX_DTYPE_F16) {
+  if (dtype != FX_DTYPE_F32 && dtype != FX_DTYPE_F16 && !(qu8 && dtype == FX_DTYPE_QU8)) {
     set_error("unsupported dtype %d", dtype);
     return FX_EINVAL;
   }
@@ -770,50 +855,42 @@ int probe_layout(int64_t nq, int64_t nb, int64_t ks, ProbeLayout* p) {
   return FX_OK;
 }
 
-}  // namespace
-
-}  // namespace fx
-
-using namespace fx;
-
-extern "C" {
-
-int fx_row_sqnorms(const void* x, int dtype, int64_t n, int64_t d, float* out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (n < 0 || d <= 0 || (n > 0 && (x == nullptr || out == nullptr))) {
-    set_error("fx_row_sqnorms: invalid arguments");
+// the rows of a corpus descriptor, checked (row_base is not used here)
+int corpus_rows(const fx_corpus* c, int64_t nb, int64_t ks, int metric, RowSrc* out) {
+  if (c == nullptr || (c->n > 0 && c->data == nullptr)) {
+    set_error("null corpus");
     return FX_EINVAL;
   }
-  if (dtype != FX_DTYPE_F32 && dtype != FX_DTYPE_F16) {
-    set_error("unsupported dtype %d", dtype);
-    return FX_EINVAL;
-  }
-  if (n == 0) return FX_OK;
-  const dim3 grid((unsigned)((n + 3) / 4));
-  if (dtype == FX_DTYPE_F32)
-    hipLaunchKernelGGL(rownorm_kernel<float>, grid, dim3(256), 0, stream,
-                       reinterpret_cast<const float*>(x), n, (int)d, 0, out);
-  else
-    hipLaunchKernelGGL(rownorm_kernel<_Float16>, grid, dim3(256), 0, stream,
-                       reinterpret_cast<const _Float16*>(x), n, (int)d, 0, out);
-  return check_launch("rownorm_kernel");
-}
-
-int fx_code_assign_workspace_bytes(int64_t n, int64_t d, int64_t nb, int64_t ks, size_t* out) {
-  if (out == nullptr || n < 0 || d <= 0 || nb <= 0 || ks <= 0) {
-    set_error("fx_code_assign_workspace_bytes: invalid arguments");
-    return FX_EINVAL;
-  }
-  *out = assign_layout(1, n, nb, ks, d).total;
+  int rc = validate_code(c->n, c->d, c->dtype, nb, ks, metric, true);
+  if (rc) return rc;
+  rc = validate_quant(*c);
+  if (rc) return rc;
+  const bool q = c->dtype == FX_DTYPE_QU8;
+  *out = RowSrc{c->data, c->dtype, q ? c->scale : 1.f, q ? (int)c->zero_point : 0};
   return FX_OK;
 }
 
-int fx_code_assign(const void* x, int dtype, int64_t n, int64_t d, const float* codewords,
-                   int64_t nb, int64_t ks, int metric, void* ws, size_t ws_bytes,
-                   int32_t* out_index, int64_t* out_code, float* out_dist, void* stream_) {
+int run_rownorm(const RowSrc& src, int64_t n, int64_t d, int mode, float* out, hipStream_t st) {
+  const dim3 grid((unsigned)((n + 3) / 4));
+  if (src.dtype == FX_DTYPE_F32)
+    hipLaunchKernelGGL(rownorm_kernel<float>, grid, dim3(256), 0, st,
+                       reinterpret_cast<const float*>(src.x), n, (int)d, mode, out, 1.f, 0);
+  else if (src.dtype == FX_DTYPE_F16)
+    hipLaunchKernelGGL(rownorm_kernel<_Float16>, grid, dim3(256), 0, st,
+                       reinterpret_cast<const _Float16*>(src.x), n, (int)d, mode, out, 1.f, 0);
+  else
+    hipLaunchKernelGGL(rownorm_kernel<uint8_t>, grid, dim3(256), 0, st,
+                       reinterpret_cast<const uint8_t*>(src.x), n, (int)d, mode, out, src.scale,
+                       src.zp);
+  return check_launch("rownorm_kernel");
+}
+
+// fx_code_assign / fx_code_assign_ex behind their argument checks
+int code_assign(const RowSrc& src, int64_t n, int64_t d, const float* codewords, int64_t nb,
+                int64_t ks, int metric, void* ws, size_t ws_bytes, int32_t* out_index,
+                int64_t* out_code, float* out_dist, void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  int rc = validate_code(n, d, dtype, nb, ks, metric);
-  if (rc) return rc;
+  int rc;
   if (composite_count(nb, ks) < 0 && out_code != nullptr) {
     set_error("composite code %lld^%lld does not fit 31 bits", (long long)ks, (long long)nb);
     return FX_EUNSUPPORTED;
@@ -825,7 +902,7 @@ int fx_code_assign(const void* x, int dtype, int64_t n, int64_t d, const float* 
   }
   if (n == 0) return FX_OK;
   char* w = reinterpret_cast<char*>(ws);
-  rc = run_assign(x, dtype, 1, n, d, codewords, nb, ks, metric, w, l, stream);
+  rc = run_assign(src, 1, n, d, codewords, nb, ks, metric, w, l, stream);
   if (rc) return rc;
   hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
                      reinterpret_cast<const uint64_t*>(w + l.off_keys), n, (int)nb, (int)ks,
@@ -833,23 +910,12 @@ int fx_code_assign(const void* x, int dtype, int64_t n, int64_t d, const float* 
   return check_launch("finalize_kernel");
 }
 
-int fx_kmeans_step_workspace_bytes(int64_t nb, int64_t bs, int64_t d, int64_t ks, size_t* out) {
-  if (out == nullptr || nb <= 0 || bs <= 0 || d <= 0 || ks <= 0) {
-    set_error("fx_kmeans_step_workspace_bytes: invalid arguments");
-    return FX_EINVAL;
-  }
-  const AssignLayout l = assign_layout(nb, bs, 1, ks, d);
-  *out = l.total + align256((size_t)nb * bs * 4) * 2;
-  return FX_OK;
-}
-
-int fx_kmeans_step(const void* sample, int dtype, int64_t nb, int64_t bs, int64_t d,
-                   float* codewords, int64_t ks, int metric, void* ws, size_t ws_bytes,
-                   void* stream_) {
+// fx_kmeans_step / fx_kmeans_step_ex behind their argument checks
+int kmeans_step(const RowSrc& src, int64_t nb, int64_t bs, int64_t d, float* codewords,
+                int64_t ks, int metric, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  int rc = validate_code(nb * bs, d, dtype, nb, ks, metric);
-  if (rc) return rc;
-  if (bs <= 0 || sample == nullptr || codewords == nullptr) {
+  int rc;
+  if (bs <= 0 || src.x == nullptr || codewords == nullptr) {
     set_error("fx_kmeans_step: invalid arguments");
     return FX_EINVAL;
   }
@@ -873,18 +939,11 @@ int fx_kmeans_step(const void* sample, int dtype, int64_t nb, int64_t bs, int64_
                        codewords, rows, (int)d);
     rc = check_launch("normalize_kernel");
     if (rc) return rc;
-    const dim3 grid((unsigned)((nb * bs + 3) / 4));
-    if (dtype == FX_DTYPE_F32)
-      hipLaunchKernelGGL(rownorm_kernel<float>, grid, dim3(256), 0, stream,
-                         reinterpret_cast<const float*>(sample), nb * bs, (int)d, 1, rnorm);
-    else
-      hipLaunchKernelGGL(rownorm_kernel<_Float16>, grid, dim3(256), 0, stream,
-                         reinterpret_cast<const _Float16*>(sample), nb * bs, (int)d, 1, rnorm);
-    rc = check_launch("rownorm_kernel");
+    rc = run_rownorm(src, nb * bs, d, 1, rnorm, stream);
     if (rc) return rc;
   }
   // argmin over each codebook for its own sample slice (vmap over codebooks)
-  rc = run_assign(sample, dtype, nb, bs, d, codewords, 1, ks, metric, w, l, stream);
+  rc = run_assign(src, nb, bs, d, codewords, 1, ks, metric, w, l, stream);
   if (rc) return rc;
   hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((nb * bs + 255) / 256)), dim3(256), 0,
                      stream, reinterpret_cast<const uint64_t*>(w + l.off_keys), nb * bs, 1,
@@ -892,17 +951,104 @@ int fx_kmeans_step(const void* sample, int dtype, int64_t nb, int64_t bs, int64_
   rc = check_launch("finalize_kernel");
   if (rc) return rc;
   const dim3 grid((unsigned)ks, (unsigned)nb);
-  if (dtype == FX_DTYPE_F32)
+  const float* rn = cosine ? rnorm : nullptr;
+  const int cos = cosine ? 1 : 0;
+  if (src.dtype == FX_DTYPE_F32)
     hipLaunchKernelGGL(update_kernel<float>, grid, dim3(kUpdThreads), 0, stream,
-                       reinterpret_cast<const float*>(sample), bs, (int)d, assign,
-                       cosine ? rnorm : nullptr, codewords, (int)ks, cosine ? 1 : 0);
-  else
+                       reinterpret_cast<const float*>(src.x), bs, (int)d, assign, rn, codewords,
+                       (int)ks, cos, 1.f, 0);
+  else if (src.dtype == FX_DTYPE_F16)
     hipLaunchKernelGGL(update_kernel<_Float16>, grid, dim3(kUpdThreads), 0, stream,
-                       reinterpret_cast<const _Float16*>(sample), bs, (int)d, assign,
-                       cosine ? rnorm : nullptr, codewords, (int)ks, cosine ? 1 : 0);
+                       reinterpret_cast<const _Float16*>(src.x), bs, (int)d, assign, rn,
+                       codewords, (int)ks, cos, 1.f, 0);
+  else
+    hipLaunchKernelGGL(update_kernel<uint8_t>, grid, dim3(kUpdThreads), 0, stream,
+                       reinterpret_cast<const uint8_t*>(src.x), bs, (int)d, assign, rn, codewords,
+                       (int)ks, cos, src.scale, src.zp);
   return check_launch("update_kernel");
 }
 
+}  // namespace
+
+}  // namespace fx
+
+using namespace fx;
+
+extern "C" {
+
+int fx_row_sqnorms(const void* x, int dtype, int64_t n, int64_t d, float* out, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (n < 0 || d <= 0 || (n > 0 && (x == nullptr || out == nullptr))) {
+    set_error("fx_row_sqnorms: invalid arguments");
+    return FX_EINVAL;
+  }
+  if (dtype != FX_DTYPE_F32 && dtype != FX_DTYPE_F16) {
+    set_error("unsupported dtype %d", dtype);
+    return FX_EINVAL;
+  }
+  if (n == 0) return FX_OK;
+  return run_rownorm(RowSrc{x, dtype, 1.f, 0}, n, d, 0, out, stream);
+}
+
+int fx_code_assign_workspace_bytes(int64_t n, int64_t d, int64_t nb, int64_t ks, size_t* out) {
+  if (out == nullptr || n < 0 || d <= 0 || nb <= 0 || ks <= 0) {
+    set_error("fx_code_assign_workspace_bytes: invalid arguments");
+    return FX_EINVAL;
+  }
+  *out = assign_layout(1, n, nb, ks, d).total;
+  return FX_OK;
+}
+
+int fx_code_assign(const void* x, int dtype, int64_t n, int64_t d, const float* codewords,
+                   int64_t nb, int64_t ks, int metric, void* ws, size_t ws_bytes,
+                   int32_t* out_index, int64_t* out_code, float* out_dist, void* stream) {
+  int rc = validate_code(n, d, dtype, nb, ks, metric);
+  if (rc) return rc;
+  return code_assign(RowSrc{x, dtype, 1.f, 0}, n, d, codewords, nb, ks, metric, ws, ws_bytes,
+                     out_index, out_code, out_dist, stream);
+}
+
+int fx_code_assign_ex(const fx_corpus* c, const float* codewords, int64_t nb, int64_t ks,
+                      int metric, void* ws, size_t ws_bytes, int32_t* out_index,
+                      int64_t* out_code, float* out_dist, void* stream) {
+  RowSrc src;
+  int rc = corpus_rows(c, nb, ks, metric, &src);
+  if (rc) return rc;
+  return code_assign(src, c->n, c->d, codewords, nb, ks, metric, ws, ws_bytes, out_index,
+                     out_code, out_dist, stream);
+}
+int fx_kmeans_step_workspace_bytes(int64_t nb, int64_t bs, int64_t d, int64_t ks, size_t* out) {
+  if (out == nullptr || nb <= 0 || bs <= 0 || d <= 0 || ks <= 0) {
+    set_error("fx_kmeans_step_workspace_bytes: invalid arguments");
+    return FX_EINVAL;
+  }
+  const AssignLayout l = assign_layout(nb, bs, 1, ks, d);
+  *out = l.total + align256((size_t)nb * bs * 4) * 2;
+  return FX_OK;
+}
+
+int fx_kmeans_step(const void* sample, int dtype, int64_t nb, int64_t bs, int64_t d,
+                   float* codewords, int64_t ks, int metric, void* ws, size_t ws_bytes,
+                   void* stream) {
+  int rc = validate_code(nb * bs, d, dtype, nb, ks, metric);
+  if (rc) return rc;
+  return kmeans_step(RowSrc{sample, dtype, 1.f, 0}, nb, bs, d, codewords, ks, metric, ws,
+                     ws_bytes, stream);
+}
+
+int fx_kmeans_step_ex(const fx_corpus* sample, int64_t nb, float* codewords, int64_t ks,
+                      int metric, void* ws, size_t ws_bytes, void* stream) {
+  RowSrc src;
+  int rc = corpus_rows(sample, nb, ks, metric, &src);
+  if (rc) return rc;
+  if (nb <= 0 || sample->n % nb != 0) {
+    set_error("fx_kmeans_step_ex: %lld sample rows do not split into %lld slices",
+              (long long)sample->n, (long long)nb);
+    return FX_EINVAL;
+  }
+  return kmeans_step(src, nb, sample->n / nb, sample->d, codewords, ks, metric, ws, ws_bytes,
+                     stream);
+}
 int fx_code_probe_workspace_bytes(int64_t nq, int64_t nb, int64_t ks, size_t* out) {
   if (out == nullptr || nq <= 0 || nb <= 0 || ks <= 0) {
     set_error("fx_code_probe_workspace_bytes: invalid arguments");

@@ -958,41 +958,82 @@ class Engine:
                                                   self._stream()))
         return out
 
-    def code_assign(self, x: torch.Tensor, codewords: torch.Tensor, metric: int,
-                    index: bool = False, code: bool = True, dist: bool = False
+    @staticmethod
+    def _code_rows(x: "torch.Tensor | Shard", scale: float, zero_point: int
+                   ) -> Tuple[torch.Tensor, int, float, int]:
+        """Rows of the coded index -> (tensor, C-ABI dtype, scale, zero point).
+        A Shard brings its own map; a uint8 tensor is quint8 codes under
+        (scale, zero_point).  Any other dtype than float32 / float16 / uint8 is
+        a TypeError (the kernels would read the buffer at the wrong width)."""
+        if isinstance(x, Shard):
+            x, scale, zero_point = x.data, x.scale, x.zero_point
+        if x.dtype == torch.float32:
+            return x, _lib.DTYPE_F32, 1.0, 0
+        if x.dtype == torch.float16:
+            return x, _lib.DTYPE_F16, 1.0, 0
+        if x.dtype == torch.uint8:
+            return x, _lib.DTYPE_QU8, float(scale), int(zero_point)
+        raise TypeError(f"the coded index reads float32, float16 or uint8 (quint8) rows, "
+                        f"got {x.dtype}")
+
+    def code_assign(self, x: "torch.Tensor | Shard", codewords: torch.Tensor, metric: int,
+                    index: bool = False, code: bool = True, dist: bool = False,
+                    scale: float = 1.0, zero_point: int = 0
                     ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor],
                                Optional[torch.Tensor]]:
         """fx_code_assign: nearest codeword of every row of x [n, D] (f32/f16, on
-        this device) in every codebook of codewords [nb, ks, D] (f32).  Returns
-        (index [n, nb] int32, code [n] int64, dist [n, nb] f32), each or None."""
+        this device) in every codebook of codewords [nb, ks, D] (f32).  A Shard
+        of quint8 codes, or a uint8 tensor with its ``scale`` and
+        ``zero_point``, goes through fx_code_assign_ex (dequantised in the
+        kernel: the same bits as the f32 assign over the dequantised rows).
+        Returns (index [n, nb] int32, code [n] int64, dist [n, nb] f32), each
+        or None."""
+        x, dt, scale, zero_point = self._code_rows(x, scale, zero_point)
         nb, ks, d = codewords.shape
         n = x.shape[0]
         cw = codewords.to(self.device, torch.float32).contiguous()
-        dt = _lib.DTYPE_F32 if x.dtype == torch.float32 else _lib.DTYPE_F16
         oi = torch.empty((n, nb), dtype=torch.int32, device=self.device) if index else None
         oc = torch.empty(n, dtype=torch.int64, device=self.device) if code else None
         od = torch.empty((n, nb), dtype=torch.float32, device=self.device) if dist else None
         with self.lock:
             ws = self._workspace(_lib.code_assign_workspace_bytes(n, d, nb, ks))
-            _lib.check(_lib.load().fx_code_assign(
-                _ptr(x), dt, n, d, _ptr(cw), nb, ks, metric, _ptr(ws), ws.numel(), _ptr(oi),
-                _ptr(oc), _ptr(od), self._stream()))
+            if dt == _lib.DTYPE_QU8:
+                c = _lib.Corpus(x.data_ptr(), dt, n, d, 0, scale, zero_point)
+                _lib.check(_lib.load().fx_code_assign_ex(
+                    ctypes.byref(c), _ptr(cw), nb, ks, metric, _ptr(ws), ws.numel(), _ptr(oi),
+                    _ptr(oc), _ptr(od), self._stream()))
+            else:
+                _lib.check(_lib.load().fx_code_assign(
+                    _ptr(x), dt, n, d, _ptr(cw), nb, ks, metric, _ptr(ws), ws.numel(), _ptr(oi),
+                    _ptr(oc), _ptr(od), self._stream()))
         return oi, oc, od
 
-    def kmeans_step(self, sample: torch.Tensor, codewords: torch.Tensor, metric: int) -> None:
-        """fx_kmeans_step: sample [nb, bs, D] (f32/f16), codewords [nb, ks, D] f32
-        contiguous on this device, updated in place (coder.py:53-65 under vmap)."""
-        nb, bs, d = sample.shape
-        ks = codewords.shape[1]
+    def kmeans_step(self, sample: "torch.Tensor | Shard", codewords: torch.Tensor, metric: int,
+                    scale: float = 1.0, zero_point: int = 0) -> None:
+        """fx_kmeans_step: sample [nb, bs, D] (f32/f16; or [nb * bs, D]),
+        codewords [nb, ks, D] f32 contiguous on this device, updated in place
+        (coder.py:53-65 under vmap).  quint8 codes (a Shard, or a uint8 tensor
+        with ``scale`` and ``zero_point``) go through fx_kmeans_step_ex."""
+        sample, dt, scale, zero_point = self._code_rows(sample, scale, zero_point)
+        nb, ks = codewords.shape[0], codewords.shape[1]
+        d = sample.shape[-1]
+        if sample.numel() % (nb * d):
+            raise ValueError(f"sample {tuple(sample.shape)} does not split into {nb} slices")
+        bs = sample.numel() // (nb * d)
         if not (codewords.is_contiguous() and codewords.dtype == torch.float32
                 and codewords.device == self.device):
             raise ValueError("codewords must be a contiguous float32 tensor on the device")
-        dt = _lib.DTYPE_F32 if sample.dtype == torch.float32 else _lib.DTYPE_F16
         with self.lock:
             ws = self._workspace(_lib.kmeans_workspace_bytes(nb, bs, d, ks))
-            _lib.check(_lib.load().fx_kmeans_step(
-                _ptr(sample), dt, nb, bs, d, _ptr(codewords), ks, metric, _ptr(ws), ws.numel(),
-                self._stream()))
+            if dt == _lib.DTYPE_QU8:
+                c = _lib.Corpus(sample.data_ptr(), dt, nb * bs, d, 0, scale, zero_point)
+                _lib.check(_lib.load().fx_kmeans_step_ex(
+                    ctypes.byref(c), nb, _ptr(codewords), ks, metric, _ptr(ws), ws.numel(),
+                    self._stream()))
+            else:
+                _lib.check(_lib.load().fx_kmeans_step(
+                    _ptr(sample), dt, nb, bs, d, _ptr(codewords), ks, metric, _ptr(ws),
+                    ws.numel(), self._stream()))
 
     def code_probe(self, cw_dist: torch.Tensor, probes: int, sel: bool = True
                    ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:

@@ -113,15 +113,20 @@ def shards(parts, column: str, devs) -> List[Tuple[_engine.Shard, int, int]]:
 
 
 def gather_rows(shard_list: Sequence[_engine.Shard], rows: np.ndarray,
-                device: torch.device) -> torch.Tensor:
-    """Rows (global, ascending) of the resident shards, in order, on ``device``."""
+                device: torch.device, dequantize: bool = False) -> torch.Tensor:
+    """Rows (global, ascending) of the resident shards, in order, on ``device``.
+    ``dequantize``: quint8 codes come back as their f32 values, each shard
+    under its own map (scale * (code - zero_point), QUInt8NDArray.dequantize)."""
     rows = np.asarray(rows, dtype=np.int64)
     out = []
     for s in shard_list:
         lo, hi = np.searchsorted(rows, [s.row_base, s.row_base + s.n])
         if hi > lo:
             idx = torch.from_numpy(rows[lo:hi] - s.row_base).to(s.data.device)
-            out.append(s.data.index_select(0, idx).to(device))
+            g = s.data.index_select(0, idx)
+            if dequantize and g.dtype == torch.uint8:
+                g = (g.to(torch.float32) - s.zero_point) * s.scale
+            out.append(g.to(device))
     if not out:
         raise ValueError("no rows selected")
     return torch.cat(out) if len(out) > 1 else out[0]

@@ -22,6 +22,13 @@ Mirrors src/fenix/io/coder/coder.py of the reference:
   argmin (``fx_code_assign``), otherwise composite scores + sort
   (``fx_code_probe``); ties in (score, code) order.
 
+A quint8 tensor column (ex/arrow/quint8) is trained and encoded from its
+1-byte codes, dequantised in the kernels (``fx_kmeans_step_ex`` /
+``fx_code_assign_ex``): the same codewords and codes, bit for bit, as the
+float32 column of the dequantised rows.  ``call`` encodes a
+``QUInt8TensorArray`` (or a table's quint8 column) with that array's own
+map; float targets stay float (queries are never coded).
+
 Differences, all deliberate: the file stores the column type as a serialized
 Arrow schema (bytes) instead of a pickled ``pa.DataType`` so it loads with
 ``torch.load(weights_only=True)`` (a reference-written coding file is refused
@@ -192,17 +199,25 @@ def make(root: str, name: str, source: str | Sequence[str], column: str, config:
     devs = _engine.devices()
     shard_list = [s for s, _, _ in _resident.shards(parts, column, devs)]
     dev = shard_list[0].data.device if shard_list else devs[0]
+    # quint8 codes train as codes while every shard shares one map; sources
+    # with different maps are dequantised shard by shard (the same f32 rows,
+    # so the same codewords, through the f32 step)
+    maps = {(s.scale, s.zero_point) for s in shard_list}
+    as_codes = len(maps) == 1
+    scale, zp = next(iter(maps)) if as_codes else (1.0, 0)
     with torch.cuda.device(dev):
         eng = Engine.get(dev)
-        coding = _resident.gather_rows(shard_list, rows, dev).to(torch.float32)
+        coding = _resident.gather_rows(shard_list, rows, dev, dequantize=True).to(torch.float32)
         coding = coding.reshape(nb, ks, -1).contiguous()
         for _ in range(epochs):
             step = nb * bs
             batch_rows = np.random.permutation(n)
             batch_rows = batch_rows[: batch_rows.size // step * step]
             for idx in np.array_split(batch_rows, batch_rows.size // step):
-                sample = _resident.gather_rows(shard_list, np.sort(idx), dev)
-                eng.kmeans_step(sample.reshape(nb, bs, -1).contiguous(), coding, m)
+                sample = _resident.gather_rows(shard_list, np.sort(idx), dev,
+                                               dequantize=not as_codes)
+                eng.kmeans_step(sample.reshape(nb, bs, -1).contiguous(), coding, m,
+                                scale=scale, zero_point=zp)
         tensor = coding.cpu()
 
     path = _path(root, name)
@@ -236,16 +251,26 @@ def drop(root: str, name: str) -> None:
 
 
 # ---------------------------------------------------------------------- codes
-def codes(target: Tensor, coding: Coding, maxval: int | None) -> Tensor:
+def codes(target: Tensor, coding: Coding, maxval: int | None,
+          qmap: Tuple[float, int] | None = None) -> Tensor:
     """[m, maxval] (or [m, ks^nb]) composite codes on the GPU, ascending by
-    (composite score, code)."""
+    (composite score, code).  ``qmap``: the target is uint8 quint8 codes under
+    this (scale, zero point)."""
     nb = int(coding["config"]["num_codebooks"])
     ks = int(coding["config"]["codebook_size"])
     m = metric_id(coding["config"]["metric"])
     tensor = coding["tensor"]
     eng = Engine.get()
-    x = _rows(target.reshape(-1, tensor.shape[-1]), eng.device)
+    target = target.reshape(-1, tensor.shape[-1])
     cw = tensor.to(eng.device, torch.float32).contiguous()
+    if qmap is not None:
+        q = target.to(eng.device, torch.uint8).contiguous()
+        if maxval == 1:
+            _, code, _ = eng.code_assign(q, cw, m, scale=qmap[0], zero_point=qmap[1])
+            return code[:, None]
+        x = _dequantize(q, *qmap)  # the composite sort scores f32 rows
+    else:
+        x = _rows(target, eng.device)
     if maxval == 1:  # independent terms: the composite argmin is per codebook
         _, code, _ = eng.code_assign(x, cw, m)
         return code[:, None]
@@ -258,6 +283,45 @@ def codes(target: Tensor, coding: Coding, maxval: int | None) -> Tensor:
     d = eng.distances(Shard(cw.reshape(nb * ks, -1), 0), x.to(torch.float32), m)
     out, _, _ = eng.code_probe(d.reshape(-1, nb, ks), p, sel=False)
     return out
+
+
+def _dequantize(codes: Tensor, scale: float, zero_point: int) -> Tensor:
+    """QUInt8NDArray.dequantize in f32: scale * (code - zero_point), one rounding."""
+    return (codes.to(torch.float32) - zero_point) * scale
+
+
+def target_rows(target, column: pa.DataType) -> Tuple[Tensor, Tuple[float, int] | None]:
+    """Normalise ``call``'s target -> (rows, map).  A quint8 tensor array (or
+    the quint8 column of the coding's type in a table) yields its uint8 codes
+    and its own type's (scale, zero point); ndarray, Tensor and
+    ``fixed_size_list<float>`` targets stay float, with no map."""
+    if isinstance(target, pa.Table):  # the column of the coding's type
+        names = [f.name for f in target.schema if f.type == column]
+        if not names:
+            raise KeyError(f"no column of type {column} in the target table")
+        target = target.column(names[0])
+
+    if isinstance(target, pa.ChunkedArray):
+        target = target.combine_chunks()
+
+    if isinstance(target, pa.ExtensionArray):
+        from ..ex.arrow import quint8
+
+        if not quint8.is_quint8(target.type):
+            raise TypeError(f"unsupported target type {target.type}")
+        rows = torch.from_numpy(np.array(target.codes()))  # writable copy
+        return rows, (float(target.type.scale), int(target.type.shift))
+
+    if isinstance(target, pa.Array):
+        from . import torch as io_torch
+
+        target = io_torch.from_arrow(target)
+
+    if isinstance(target, np.ndarray):
+        target = torch.from_numpy(target)
+
+    assert isinstance(target, Tensor)
+    return target, None
 
 
 def call(
@@ -273,28 +337,9 @@ def call(
     if isinstance(coding, tuple):
         coding = load(*coding)
 
-    column = coding["column"]
+    rows, qmap = target_rows(target, coding["column"])
 
-    if isinstance(target, pa.Table):  # the column of the coding's type
-        names = [f.name for f in target.schema if f.type == column]
-        if not names:
-            raise KeyError(f"no column of type {column} in the target table")
-        target = target.column(names[0]).combine_chunks()
-
-    if isinstance(target, pa.ChunkedArray):
-        target = target.combine_chunks()
-
-    if isinstance(target, pa.Array):
-        from . import torch as io_torch
-
-        target = io_torch.from_arrow(target)
-
-    if isinstance(target, np.ndarray):
-        target = torch.from_numpy(target)
-
-    assert isinstance(target, Tensor)
-
-    data = codes(target, coding, maxval).cpu()
+    data = codes(rows, coding, maxval, qmap).cpu()
 
     if return_torch:
         return data

@@ -36,7 +36,8 @@ behaviour:
 ``<root>/indexes/<source>/<column>/<name>.arrow`` holding one int64
 ``__CODED_ID__`` per row, written in the source's batch layout; ``make``
 encodes the HBM-resident column with fx_code_assign (MFMA nearest codeword per
-codebook) instead of the per-batch pyarrow UDF (index.py:46-49).
+codebook; fx_code_assign_ex over the 1-byte codes of a quint8 column, each
+shard under its own map) instead of the per-batch pyarrow UDF (index.py:46-49).
 
 What changes underneath: the corpus column is resident in HBM (engine.CACHE)
 instead of re-read and scanned per chunk by a Python UDF, top-k is fused into
@@ -307,7 +308,8 @@ def _encode(root: str, source: str, column: str, code: coder.Coding) -> tuple:
     for s, _, start in _resident.shards(parts, column, _engine.devices()):
         dev = s.data.device
         with torch.cuda.device(dev):
-            _, c, _ = _engine.Engine.get(dev).code_assign(s.data, code["tensor"], m)
+            # the shard brings its own quint8 map (sources may differ in scale)
+            _, c, _ = _engine.Engine.get(dev).code_assign(s, code["tensor"], m)
             out[start : start + s.n] = c.cpu().numpy()
     return t, out
 

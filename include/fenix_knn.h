@@ -561,6 +561,24 @@ int fx_knn_search_ex(const fx_corpus* c, const int32_t* rows, int64_t nrows,
 int fx_knn_distances_ex(const fx_corpus* c, const float* queries, int64_t nq, int metric,
                         const uint32_t* mask, float* out, void* stream);
 
+/*
+ * The coded index over a descriptor (added within 1.4; fx_version() is still
+ * 104): fx_code_assign / fx_kmeans_step for FX_DTYPE_F32, F16 and QU8 rows.
+ * QU8 rows are read as their 1-byte codes and dequantised while they are
+ * staged, scale * (float)(code - zero_point) in f32 with one rounding, so
+ * indices, codes, distance bits and trained codewords equal those of the plain
+ * entry points over the dequantised f32 rows.  Any code 0..255 is valid.
+ * row_base is ignored.  fx_kmeans_step_ex: sample->n = nb * bs rows, slice j
+ * (rows [j*bs, (j+1)*bs)) trains codebook j.  Workspaces: the shape-only
+ * fx_code_assign_workspace_bytes / fx_kmeans_step_workspace_bytes.  The plain
+ * entry points keep refusing FX_DTYPE_QU8 (FX_EINVAL): they carry no map.
+ */
+int fx_code_assign_ex(const fx_corpus* c, const float* codewords, int64_t nb, int64_t ks,
+                      int metric, void* ws, size_t ws_bytes, int32_t* out_index,
+                      int64_t* out_code, float* out_dist, void* stream);
+int fx_kmeans_step_ex(const fx_corpus* sample, int64_t nb, float* codewords, int64_t ks,
+                      int metric, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------ multi-GPU exchange
  * Single-process communicator over RCCL (xGMI): one rank per listed device
  * (a serving process driving every GPU of a node).  fx_allgather_topk gathers
