@@ -167,6 +167,23 @@ static int next_pow2(int v) {
   return p;
 }
 
+// What one merge_kernel workgroup may ask for: allow_lds lifts the dynamic
+// limit to the CU's 160 KB (the kernel has no static __shared__).
+constexpr size_t kMergeLdsBudget = 160 * 1024;
+
+// Dynamic LDS of one level: MergeShared and the result area (P2 slots: the
+// final level bitonic-sorts it), then the G input lists (the input area
+// doubles as the rank-sort output on the final level, hence at least k).
+// plan_merge sizes G by it and run_merge launches with it.
+static size_t merge_fixed_bytes(int64_t k) {
+  const int64_t P2 = next_pow2((int)k);
+  return sizeof(MergeShared) + (size_t)(P2 > k ? P2 : k) * 8;
+}
+
+static size_t merge_lds_bytes(int64_t G, int64_t klen, int64_t k) {
+  return merge_fixed_bytes(k) + (size_t)(G * klen > k ? G * klen : k) * 8;
+}
+
 int plan_merge(int64_t nq, int64_t nlists, int64_t kin, int64_t k, MergePlan* p) {
   if (kin > kMergeEntries / 2 || k > kMergeEntries / 2) {
     set_error("merge list length %lld / k %lld exceeds %lld", (long long)kin, (long long)k,
@@ -190,8 +207,20 @@ int plan_merge(int64_t nq, int64_t nlists, int64_t kin, int64_t k, MergePlan* p)
       const int64_t g = diag_env("FX_MERGE_GROUP", 0);
       if (g >= 2 && g * klen <= kMergeEntries) G = g;
     }
+    // the result area comes out of the same LDS as the lists: above k = 2048
+    // (the probe merge; every search has k <= 1024) kMergeEntries of input
+    // no longer fit beside it, so the level folds fewer lists
+    const int64_t room = (int64_t)(kMergeLdsBudget - merge_fixed_bytes(k)) / 8;
+    if (G * klen > room) G = room / klen;
     if (G < 2) G = 2;
     if (G > lists) G = lists;
+    // (even two lists too many: long lists with k above 4096)
+    if (merge_lds_bytes(G, klen, k) > kMergeLdsBudget) {
+      set_error("merge of %lld lists of %lld for k %lld needs %zu bytes of LDS, above %zu",
+                (long long)G, (long long)klen, (long long)k, merge_lds_bytes(G, klen, k),
+                kMergeLdsBudget);
+      return FX_EUNSUPPORTED;
+    }
     const int64_t next = (lists + G - 1) / G;
     p->group[p->levels] = G;
     p->lists[p->levels] = lists;
@@ -224,10 +253,7 @@ int run_merge(const MergePlan& p, const uint64_t* in, int64_t nq, int64_t k, voi
     const int64_t blocks = (lists + G - 1) / G;
     const bool fin = lv == p.levels - 1;
     uint64_t* dst = fin ? nullptr : bufs[lv & 1];
-    const int rcap = P2 > k ? P2 : (int)k;
-    // the input area doubles as the rank-sort output on the final level
-    const int64_t sin = G * klen > k ? G * klen : k;
-    const size_t smem = sizeof(MergeShared) + (size_t)rcap * 8 + (size_t)sin * 8;
+    const size_t smem = merge_lds_bytes(G, klen, k);
     if (int rc = allow_lds((const void*)merge_kernel)) return rc;
     for (int64_t q0 = 0; q0 < nq; q0 += 65535) {
       const int64_t qn = (nq - q0) < 65535 ? (nq - q0) : 65535;
