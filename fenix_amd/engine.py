@@ -950,7 +950,11 @@ class Engine:
 
     # ------------------------------------------------------------ coded index
     def row_sqnorms(self, x: torch.Tensor) -> torch.Tensor:
-        """fx_row_sqnorms: [n] f32 sum of squares of each row of x [n, D]."""
+        """fx_row_sqnorms: [n] f32 sum of squares of each row of x [n, D]
+        (float32 or float16; anything else is a TypeError: the kernel would
+        read the buffer at the wrong width)."""
+        if x.dtype not in (torch.float32, torch.float16):
+            raise TypeError(f"row_sqnorms reads float32 or float16 rows, got {x.dtype}")
         out = torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
         dt = _lib.DTYPE_F32 if x.dtype == torch.float32 else _lib.DTYPE_F16
         with self.lock:

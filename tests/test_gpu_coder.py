@@ -67,9 +67,11 @@ def _assign_ok(x, cw, metric, got_index, got_dist=None):
 
 @pytest.mark.parametrize("metric", METRICS)
 @pytest.mark.parametrize("nb,ks,d", [(2, 8, 64), (3, 5, 48), (2, 37, 128), (1, 64, 96),
-                                     (2, 300, 64), (4, 16, 50)])
+                                     (2, 300, 64), (4, 16, 50),
+                                     # long rows: 24, 128 and 512 passes of the K-chunk loop
+                                     (2, 16, 768), (1, 8, 4096), (1, 4, 16384)])
 def test_code_assign_matches_oracle(eng, metric, nb, ks, d):
-    n = 3000
+    n = 3000 if d <= 300 else 1000
     x = O.fill_normal(n, d, seed=41, cluster=100)
     cw = O.fill_normal(nb * ks, d, seed=42).reshape(nb, ks, d)
     xt = torch.from_numpy(x).to(eng.device)
@@ -94,6 +96,18 @@ def test_code_assign_float16_and_tail_rows(eng, metric):
                                 code=False)
     torch.cuda.synchronize()
     _assign_ok(x.astype(np.float32), cw, metric, idx.cpu().numpy())
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_code_assign_float16_long_rows(eng, metric):
+    n, d, nb, ks = 1000, 1536, 2, 16  # 48 passes of the K-chunk loop over widened f16 rows
+    x = O.fill_normal(n, d, seed=49).astype(np.float16)
+    cw = O.fill_normal(nb * ks, d, seed=50).reshape(nb, ks, d)
+    xt = torch.from_numpy(x).to(eng.device)
+    idx, _, dist = eng.code_assign(xt, torch.from_numpy(cw), _lib.METRICS[metric], index=True,
+                                   code=False, dist=True)
+    torch.cuda.synchronize()
+    _assign_ok(x.astype(np.float32), cw, metric, idx.cpu().numpy(), dist.cpu().numpy())
 
 
 @pytest.mark.parametrize("metric", METRICS)
