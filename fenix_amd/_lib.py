@@ -80,6 +80,8 @@ SYMBOLS = (
     "fx_knn_search_rows",
     "fx_mask_compact_workspace_bytes",
     "fx_mask_compact",
+    "fx_pred_limits",
+    "fx_pred_eval",
     "fx_knn_search_ex_workspace_bytes",
     "fx_knn_search_ex",
     "fx_knn_search_shards_workspace_bytes",
@@ -109,7 +111,8 @@ SYMBOLS = (
 OPTIONS = ("batched", "batch_min_queries", "batch_cap", "batch_sample_ratio", "force_fallback",
            "scan_interleave", "q8_dma", "filter_image", "batch_ub_test", "single_query_image",
            "i8_max_k", "img6", "img8", "i8_sample_ratio", "i8_grow_ratio", "select_prune",
-           "scan_stream", "filter_hold", "qu8_batch_min_work", "qmask_batch_min_ratio")
+           "scan_stream", "filter_hold", "qu8_batch_min_work", "qmask_batch_min_ratio",
+           "device_filter_min_rows")
 
 _lock = threading.Lock()
 _lib = None
@@ -126,6 +129,29 @@ class Corpus(ctypes.Structure):
         ("row_base", ctypes.c_int64),
         ("scale", ctypes.c_float),
         ("zero_point", ctypes.c_int32),
+    ]
+
+
+class PredColumn(ctypes.Structure):
+    """struct fx_pred_column (include/fenix_knn.h)."""
+
+    _fields_ = [
+        ("values", ctypes.c_void_p),
+        ("valid", ctypes.c_void_p),
+        ("dtype", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class PredOp(ctypes.Structure):
+    """struct fx_pred_op (include/fenix_knn.h)."""
+
+    _fields_ = [
+        ("op", ctypes.c_int32),
+        ("column", ctypes.c_int32),
+        ("imm", ctypes.c_int64),
+        ("set_offset", ctypes.c_int32),
+        ("set_length", ctypes.c_int32),
     ]
 
 
@@ -238,6 +264,12 @@ def load() -> ctypes.CDLL:
         L.fx_mask_compact_workspace_bytes.restype = ci
         L.fx_mask_compact.argtypes = [vp, i64, vp, sz, vp, vp, vp]
         L.fx_mask_compact.restype = ci
+        pi = ctypes.POINTER(ci)
+        L.fx_pred_limits.argtypes = [pi, pi, pi, pi]
+        L.fx_pred_limits.restype = ci
+        L.fx_pred_eval.argtypes = [ctypes.POINTER(PredColumn), ci, ctypes.POINTER(PredOp), ci, vp,
+                                   i64, i64, vp, vp, vp, vp]
+        L.fx_pred_eval.restype = ci
         pc_ = ctypes.POINTER(Corpus)
         L.fx_knn_search_ex_workspace_bytes.argtypes = [pc_, i64, i64, i64, psz]
         L.fx_knn_search_ex_workspace_bytes.restype = ci
@@ -429,6 +461,13 @@ def search_shards_workspace_bytes(corpora, nq: int, k: int) -> int:
     check(load().fx_knn_search_shards_workspace_bytes(corpora, len(corpora), nq, k,
                                                       ctypes.byref(out)))
     return int(out.value)
+
+
+def pred_limits() -> dict:
+    """fx_pred_limits: the predicate program's size limits."""
+    v = [ctypes.c_int(0) for _ in range(4)]
+    check(load().fx_pred_limits(*[ctypes.byref(x) for x in v]))
+    return dict(zip(("columns", "ops", "set", "pool"), (int(x.value) for x in v)))
 
 
 def set_option(name: str, value: int) -> None:

@@ -38,6 +38,11 @@ constexpr int kSelectMaxK = 2048;
 //                        batch when one by one they would read at least this many times the
 //                        batch's bytes (host policy: engine.qmask_batch_pays; 1.23: the smallest
 //                        measured ratio from which the batch won, profiles/qmask_batch_sweep.json)
+//   device_filter_min_rows  filters the predicate compiler accepts are evaluated on the device
+//                        (fx_pred_eval) for tables of at least this many rows (host policy:
+//                        io.index.call; 10 000: the smallest measured row count, from which the
+//                        device path's median beat the host path's at every point,
+//                        profiles/filter_pushdown.json)
 #define FX_OPTIONS(FX_OPTION)                               \
   FX_OPTION(kOptBatched, "batched", 1)                      \
   FX_OPTION(kOptBatchMinQ, "batch_min_queries", 2)          \
@@ -58,7 +63,8 @@ constexpr int kSelectMaxK = 2048;
   FX_OPTION(kOptScanStream, "scan_stream", -1)             \
   FX_OPTION(kOptFilterHold, "filter_hold", 0)               \
   FX_OPTION(kOptQu8BatchMinWork, "qu8_batch_min_work", 204800000) \
-  FX_OPTION(kOptQmaskBatchMinRatio, "qmask_batch_min_ratio", 123)
+  FX_OPTION(kOptQmaskBatchMinRatio, "qmask_batch_min_ratio", 123) \
+  FX_OPTION(kOptDeviceFilterMinRows, "device_filter_min_rows", 10000)
 enum Option : int {
 #define FX_OPTION_ENUM(id, name, dflt) id,
   FX_OPTIONS(FX_OPTION_ENUM)

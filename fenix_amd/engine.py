@@ -199,6 +199,16 @@ class ScanState:
 
 
 @dataclass
+class PredColumn:
+    """A scalar column staged for fx_pred_eval (io._resident.pred_column)."""
+
+    values: torch.Tensor               # [rows] in the column's own width (strings: int32 codes)
+    valid: Optional[torch.Tensor]      # validity words from bit 0 of row 0, or None: no nulls
+    dictionary: Optional[pa.Array]     # string columns: the distinct strings, on the host
+    dtype: int                         # FX_PRED_*
+
+
+@dataclass
 class _Entry:
     key: tuple
     table: pa.Table
@@ -250,7 +260,8 @@ def _budget_bytes(dev: int) -> int:
 
 class Residency:
     """LRU accounting of the HBM held by the resident caches: staged corpus
-    shards (``CorpusCache``) and filter images (``Engine.filter_image``).
+    shards (``CorpusCache``), filter images (``Engine.filter_image``) and the
+    scalar columns row filters read (``io._resident.pred_column``).
 
     The reference holds nothing between calls (it re-maps the Arrow file per
     search, src/fenix/io/index/index.py:97); a server keeping tables resident
@@ -261,7 +272,7 @@ class Residency:
     search).  An entry in use by a running search keeps its tensors alive
     through that search's own references; eviction only drops the cache's."""
 
-    IMAGE, CORPUS = 0, 1
+    IMAGE, CORPUS, PRED = 0, 1, 2
 
     def __init__(self) -> None:
         self._lock = threading.RLock()
@@ -288,20 +299,28 @@ class Residency:
             self._items.pop(key, None)
 
     def reserve(self, need: Dict[int, int], keep: Sequence[tuple] = (),
-                kinds: Sequence[int] = (0, 1)) -> bool:
-        """Evict entries of ``kinds`` (LRU first, images before corpora) until
-        ``need`` more bytes fit every listed device's budget; False when they
-        cannot.  A filter image reserves with ``kinds=(IMAGE,)``: an optional
-        image never evicts a corpus (it could be the one it is built for).
-        The victims' callbacks run after this object's lock is released (they
-        take their cache's lock)."""
+                kinds: Sequence[int] = (0, 1, 2)) -> bool:
+        """Evict entries of ``kinds`` (LRU first within a kind) until ``need``
+        more bytes fit every listed device's budget; False when they cannot.
+        Order of the kinds: where dropping the device's predicate columns
+        alone makes the room, they go first and nothing else is touched;
+        otherwise images, then corpora, and the predicate columns last (their
+        few bytes per row would not spare a corpus).  A filter image reserves
+        with ``kinds=(IMAGE, PRED)``: an optional image never evicts a corpus
+        (it could be the one it is built for).  The victims' callbacks run
+        after this object's lock is released (they take their cache's lock)."""
         victims = []
         ok = True
         with self._lock:
             for dev, extra in need.items():
                 budget = _budget_bytes(dev)
                 used = self.used(dev)
-                for kind in [k for k in (self.IMAGE, self.CORPUS) if k in kinds]:
+                pred = sum(v[1].get(dev, 0) for k, v in self._items.items()
+                           if v[0] == self.PRED and k not in keep)
+                order = (self.IMAGE, self.CORPUS, self.PRED)
+                if used + extra - pred <= budget:  # the predicate columns alone make the room
+                    order = (self.PRED,) + order[:2]
+                for kind in [k for k in order if k in kinds]:
                     for key in [k for k, v in self._items.items()
                                 if v[0] == kind and v[1].get(dev, 0) > 0 and k not in keep]:
                         if used + extra <= budget:
@@ -512,7 +531,8 @@ class Engine:
         ib, rb = ctypes.c_size_t(0), ctypes.c_size_t(0)
         _lib.check(size_fn(n, d, ctypes.byref(ib), ctypes.byref(rb)))
         need = ib.value + rb.value
-        if not RESIDENT.reserve({self.device.index: need}, kinds=(Residency.IMAGE,)):
+        if not RESIDENT.reserve({self.device.index: need},
+                                kinds=(Residency.IMAGE, Residency.PRED)):
             return none
         free, _ = torch.cuda.mem_get_info(self.device)
         cached = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
@@ -1068,6 +1088,31 @@ class Engine:
             _lib.check(_lib.load().fx_code_mask(
                 _ptr(row_code), n, _ptr(sel), ncodes, _ptr(filter), _ptr(out), _ptr(cnt),
                 self._stream()))
+        return out, cnt
+
+    def pred_eval(self, program, columns: Sequence["PredColumn"], n: int, row0: int,
+                  and_mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """fx_pred_eval: a filter program (io.predicate.Program, or its encoded
+        (ops, pool)) over staged columns -> (bitmap [ceil(n/32)] int32 of the
+        staged rows row0 .. row0 + n - 1, kept-row count [1] int64)."""
+        if not isinstance(program, tuple):
+            program = program.encode([c.dictionary for c in columns])
+        ops, pool = program
+        ops = np.ascontiguousarray(ops)
+        pool = np.ascontiguousarray(pool, dtype=np.int64)
+        for c in columns:
+            if c.values.device != self.device or c.values.shape[0] < row0 + n:
+                raise ValueError("pred_eval: a column on another device or shorter than row0 + n")
+        cols = (_lib.PredColumn * max(1, len(columns)))(
+            *[_lib.PredColumn(_ptr(c.values), _ptr(c.valid), c.dtype, 0) for c in columns])
+        out = torch.empty(max(1, (n + 31) // 32), dtype=torch.int32, device=self.device)
+        cnt = torch.empty(1, dtype=torch.int64, device=self.device)
+        # (the library works on the current device: its set-pool slots are per device)
+        with self.lock, torch.cuda.device(self.device):
+            _lib.check(_lib.load().fx_pred_eval(
+                cols, len(columns), ops.ctypes.data_as(ctypes.POINTER(_lib.PredOp)), len(ops),
+                pool.ctypes.data if pool.size else None, n, row0, _ptr(and_mask), _ptr(out),
+                _ptr(cnt), self._stream()))
         return out, cnt
 
     def fill(self, out: torch.Tensor, seed: int, row_base: int = 0, cluster: int = 0) -> None:

@@ -6,7 +6,9 @@
 * single-chunk copies of small result columns for ``take`` (index.py:166);
 * the HBM shards of embedding columns (engine.CACHE) and of index code
   columns (``__CODED_ID__``, int64 per row) used to build probe masks on the
-  device.
+  device;
+* the scalar columns a row filter reads (``pred_column``), staged whole per
+  device for fx_pred_eval and accounted in ``engine.RESIDENT``.
 """
 
 from __future__ import annotations
@@ -21,13 +23,14 @@ import pyarrow.compute as pc
 import torch
 
 from .. import engine as _engine
-from . import arrow, table
+from . import arrow, predicate, table
 
 _lock = threading.Lock()
 _TABLES: Dict[str, Tuple[tuple, pa.Table]] = {}  # path -> (stat key, mmap'd table)
 # (version, column) -> single-chunk column; (version, column, "null") -> null slots
 _COMBINED: Dict[tuple, object] = {}
 _CODES: Dict[tuple, torch.Tensor] = {}  # (stat key, column, device) -> int64 [rows]
+_PRED: Dict[tuple, _engine.PredColumn] = {}  # (stat key, column, device) -> staged column
 
 
 def stat_key(path: str) -> tuple:
@@ -48,6 +51,9 @@ def load_table(path: str) -> Tuple[tuple, pa.Table]:
             del _COMBINED[k]
         for k in [k for k in _CODES if k[0][0] == key[0] and k[0] != key]:
             del _CODES[k]
+        for k in [k for k in _PRED if k[0][0] == key[0] and k[0] != key]:
+            del _PRED[k]
+            _engine.RESIDENT.remove(("pred",) + k)
     return key, t
 
 
@@ -145,3 +151,42 @@ def code_column(key: tuple, t: pa.Table, column: str, device: torch.device) -> t
     with _lock:
         _CODES[ck] = dev
     return dev
+
+
+def _pred_evicted(ck: tuple) -> None:
+    with _lock:
+        _PRED.pop(ck, None)
+
+
+def pred_column(key: tuple, t: pa.Table, column: str,
+                device: torch.device) -> _engine.PredColumn:
+    """A scalar column of a source as fx_pred_eval reads it, whole, resident on
+    ``device`` (cached per file version; a shard addresses it with row0 = its
+    first source row): the values in the column's own width, the validity
+    words repacked to start at bit 0 (only when the column has nulls) and, for
+    string columns, int32 codes into the distinct strings kept on the host."""
+    ck = (key, column, str(device))
+    rkey = ("pred",) + ck
+    with _lock:
+        hit = _PRED.get(ck)
+    if hit is not None:
+        _engine.RESIDENT.touch(rkey)
+        return hit
+    values, valid, dictionary = predicate.host_column(t.column(column))
+    words = predicate.pack_validity(valid) if valid is not None else None
+    need = {device.index: values.nbytes + (words.nbytes if words is not None else 0)}
+    # as CorpusCache.get: reserve evicts what it may; a column that still does
+    # not fit the budget is staged all the same (the search needs it now) and
+    # is the first to go at the next reservation
+    _engine.RESIDENT.reserve(need)
+    dtype = predicate._column_kind(t.schema.field(column).type)[1]
+    signed = {"u": "i"}.get(values.dtype.kind, values.dtype.kind) + str(values.dtype.itemsize)
+    with torch.cuda.device(device):
+        staged = _engine.PredColumn(
+            torch.from_numpy(values.view(signed)).to(device),  # the bits; dtype names the type
+            torch.from_numpy(words.view(np.int32)).to(device) if words is not None else None,
+            dictionary, dtype)
+    with _lock:
+        _PRED[ck] = staged
+    _engine.RESIDENT.add(rkey, _engine.Residency.PRED, need, lambda: _pred_evicted(ck))
+    return staged

@@ -24,7 +24,10 @@ behaviour:
 * ``select`` default = every column, then ``__DISTANCE__`` appended
   (index.py:128-129); ``assert metric is not None`` (index.py:131); an unknown
   metric raises ``ValueError()`` (coder.py:50);
-* ``filter`` (pc.Expression) restricts the rows before the scan (index.py:161);
+* ``filter`` (pc.Expression) restricts the rows before the scan (index.py:161):
+  an expression ``io.predicate`` compiles is evaluated on the device over the
+  source's resident scalar columns (fx_pred_eval), every other one by pyarrow
+  on the host; the rows kept are the same (``filter_stats``);
 * if ``maxval is not None and rows > maxval``: the ``maxval`` nearest rows,
   ascending by distance (index.py:165-168, select_k_unstable), here with the
   deterministic (distance, row) tie-break; otherwise every row in table order
@@ -58,7 +61,8 @@ import torch
 from torch import Tensor
 
 from .. import engine as _engine
-from . import _resident, arrow, coder, table
+from .. import _lib
+from . import _resident, arrow, coder, predicate, table
 
 CODE_COL: str = "__CODED_ID__"
 DIST_COL: str = "__DISTANCE__"
@@ -119,6 +123,80 @@ def _filter_mask(data: pa.Table, filter: pc.Expression) -> np.ndarray:
 
     m = ds.dataset(data).to_table(columns={"__m__": filter}).column("__m__")
     return m.fill_null(False).to_numpy(zero_copy_only=False).astype(bool)
+
+
+_stats_lock = threading.Lock()
+_FILTER_STATS = {"device": 0, "host": 0, "reasons": {}}
+
+
+def filter_stats() -> dict:
+    """How many filters were evaluated on the device (fx_pred_eval) and how
+    many by pyarrow on the host, and why the latter: {"device": n, "host": n,
+    "reasons": {reason: n}}."""
+    with _stats_lock:
+        return {"device": _FILTER_STATS["device"], "host": _FILTER_STATS["host"],
+                "reasons": dict(_FILTER_STATS["reasons"])}
+
+
+def _count_filter(reason: str | None) -> None:
+    with _stats_lock:
+        if reason is None:
+            _FILTER_STATS["device"] += 1
+        else:
+            _FILTER_STATS["host"] += 1
+            _FILTER_STATS["reasons"][reason] = _FILTER_STATS["reasons"].get(reason, 0) + 1
+
+
+def _device_filter(data: pa.Table, parts, filter: pc.Expression):
+    """The program of a filter the device evaluates, or None (and the reason
+    counted): ``FENIX_AMD_DEVICE_FILTER=0`` switches the device path off,
+    ``pa.Table`` sources, tables below the library option
+    "device_filter_min_rows" and every expression ``predicate.compile``
+    refuses keep pyarrow's evaluation."""
+    reason, program = None, None
+    if os.environ.get("FENIX_AMD_DEVICE_FILTER", "1").strip() == "0":
+        reason = "switched off"
+    elif any(path is None for path, _ in parts):
+        reason = "table source"
+    elif data.num_rows < max(1, _lib.get_option("device_filter_min_rows")):
+        reason = "below device_filter_min_rows"
+    else:
+        program, why = predicate.explain(filter, data.schema)
+        if program is None:
+            reason = "expression: " + why
+        elif any(t.schema.get_field_index(c.name) < 0
+                 or t.schema.field(c.name).type != data.schema.field(c.name).type
+                 for _, t in parts for c in program.columns):
+            reason, program = "column outside the source files", None
+    _count_filter(reason)
+    return program
+
+
+def _device_masks(program, shard_info, parts, version, want_counts: bool = True):
+    """fx_pred_eval per shard over the source's resident predicate columns.
+    -> (per-shard bitmaps, per-shard kept rows: one D2H per device; None when
+    not wanted: a probe search counts behind its own mask)."""
+    masks, cnts = [], []
+    for s, src, start in shard_info:
+        dev = s.data.device
+        with torch.cuda.device(dev):
+            cols = [_resident.pred_column(version[src], parts[src][1], c.name, dev)
+                    for c in program.columns]
+            mk, cnt = _engine.Engine.get(dev).pred_eval(program, cols, s.n, start)
+        masks.append(mk)
+        cnts.append(cnt)
+    if not want_counts:
+        return masks, None
+    counts = [0] * len(cnts)
+    by_dev = {}
+    for i, c in enumerate(cnts):
+        by_dev.setdefault(c.device, []).append(i)
+    for dev, idx in by_dev.items():
+        with torch.cuda.device(dev):
+            got = torch.cat([cnts[i] for i in idx]).cpu().numpy()
+        for i, v in zip(idx, got):
+            counts[i] = int(v)
+    return masks, counts
 
 
 def _take_chunked(col: pa.ChunkedArray, rows: np.ndarray) -> pa.Array:
@@ -452,10 +530,13 @@ def call(
     m = coder.metric_id(metric)
     _engine.value_dtype(type)
 
-    fmask = _filter_mask(data, filter) if filter is not None else None
+    program = _device_filter(data, parts, filter) if filter is not None else None
+    fmask = _filter_mask(data, filter) if filter is not None and program is None else None
     shard_info = _resident.shards(parts, column, _engine.devices())
     shards = [s for s, _, _ in shard_info]
     masks = None
+    if program is not None:
+        masks, counts = _device_masks(program, shard_info, parts, version, code is None)
     if fmask is not None:
         masks = [_engine.device_mask(fmask[s.row_base : s.row_base + s.n], s.data.device)
                  for s in shards]
@@ -464,6 +545,13 @@ def call(
             raise ValueError("a probe search needs named sources with an index")
         masks, counts, n_rows, host_mask = _probe_masks(code, q, probes, shard_info, code_parts,
                                                          masks)
+    elif program is not None:
+        n_rows = sum(counts)
+
+        def host_mask() -> np.ndarray:
+            if not masks:
+                return np.zeros(0, dtype=bool)
+            return np.concatenate([_unpack(mk, s.n) for mk, s in zip(masks, shards)])
     else:
         n_rows = int(fmask.sum()) if fmask is not None else data.num_rows
         host_mask = (lambda: fmask) if fmask is not None else None

@@ -132,6 +132,13 @@ int fx_device_count(int* out);
  *                            run one by one, they would read at least this many
  *                            times the bytes of the batch's one image pass
  *                            (host policy only; the library does not read it)
+ *   "device_filter_min_rows" 10000  the serving host evaluates a filter the
+ *                            predicate compiler accepts on the device
+ *                            (fx_pred_eval) for tables of at least this many
+ *                            rows, and through pyarrow below (host policy only;
+ *                            the default: the smallest row count measured, from
+ *                            which the device path's median call beat the host
+ *                            path's at every point, profiles/filter_pushdown.json)
  * fx_set_option: FX_EINVAL for an unknown name.  Options are read when a call
  * plans its launches; set them while no search is in flight.
  */
@@ -433,6 +440,93 @@ int fx_code_mask(const int64_t* row_code, int64_t n, const uint32_t* sel, int64_
 int fx_mask_compact_workspace_bytes(int64_t n, size_t* out_bytes);
 int fx_mask_compact(const uint32_t* mask, int64_t n, void* ws, size_t ws_bytes, int32_t* out_rows,
                     uint64_t* out_count, void* stream);
+
+/*
+ * Row predicate -> row bitmap: the filter of index.py:161 over scalar columns
+ * staged on the device, as a postfix program (the host compiles and verifies
+ * it from the pc.Expression, fenix_amd/io/predicate.py).  Bit r of out_mask
+ * (ceil(n/32) words; bits past n in the last word are zero) is the predicate
+ * on staged row row0 + r, ANDed with bit r of and_mask when that is given;
+ * out_count (nullable, one uint64 on the device, zeroed by the call): the
+ * number of set bits, as fx_code_mask.  row0 is any row >= 0 (shards start
+ * anywhere inside a source); every column holds at least row0 + n rows.
+ *
+ * A column: `values` points at staged row 0 in the dtype's own width, `valid`
+ * (nullable: no nulls) at the validity words of staged row 0 (bit i & 31 of
+ * word i >> 5 set: row i is not null).  String columns are staged as their
+ * int32 dictionary codes (FX_PRED_I32), a literal absent from the dictionary
+ * as a code no row has.
+ *
+ * An instruction: leaves push, FX_PRED_AND / OR pop two and push one,
+ * FX_PRED_NOT replaces the top.  FX_PRED_EQ..GE compare `column` with `imm`
+ * (an int64 for integer columns, compared in int64; the bits of a double for
+ * float columns, compared in double: NaN fails every ordered compare and
+ * passes !=); FX_PRED_IS_IN (integer columns) looks the value up in
+ * set_pool[set_offset, set_offset + set_length), strictly ascending;
+ * FX_PRED_IS_NULL (imm 1: a NaN is null too) and FX_PRED_IS_VALID test the
+ * validity.  Entries are (value, known) pairs: a compare of a null is unknown,
+ * is_in of a null is false, and / or are Kleene's (null or true = true, null
+ * and false = false), not keeps unknown; an unknown result drops the row.
+ *
+ * cols, ops and set_pool are HOST arrays (the first two travel as kernel
+ * arguments; the pool is checked here and copied into one of a few device
+ * slots the library allocates once per device, on `stream`).  Refused before
+ * any launch, out_mask and out_count untouched (FX_EINVAL): more than
+ * FX_PRED_MAX_COLUMNS columns or FX_PRED_MAX_OPS instructions, an unknown
+ * dtype or instruction, a column index out of range, is_in on a float column,
+ * a set slice that is empty, longer than FX_PRED_MAX_SET, past
+ * FX_PRED_MAX_POOL or not strictly ascending, stack underflow, a final depth
+ * other than 1.  fx_pred_limits reports the four limits (each pointer
+ * nullable).  The host routes a filter here from option
+ * "device_filter_min_rows" rows on.
+ */
+#define FX_PRED_MAX_COLUMNS 8
+#define FX_PRED_MAX_OPS 32
+#define FX_PRED_MAX_SET 4096
+#define FX_PRED_MAX_POOL 8192
+
+#define FX_PRED_I8 0
+#define FX_PRED_I16 1
+#define FX_PRED_I32 2
+#define FX_PRED_I64 3
+#define FX_PRED_U8 4
+#define FX_PRED_U16 5
+#define FX_PRED_U32 6
+#define FX_PRED_F32 7
+#define FX_PRED_F64 8
+
+#define FX_PRED_EQ 0
+#define FX_PRED_NE 1
+#define FX_PRED_LT 2
+#define FX_PRED_LE 3
+#define FX_PRED_GT 4
+#define FX_PRED_GE 5
+#define FX_PRED_IS_IN 6
+#define FX_PRED_IS_NULL 7
+#define FX_PRED_IS_VALID 8
+#define FX_PRED_AND 9
+#define FX_PRED_OR 10
+#define FX_PRED_NOT 11
+
+typedef struct fx_pred_column {
+  const void* values;     /* device, staged row 0 */
+  const uint32_t* valid;  /* device, validity words of staged row 0, or NULL */
+  int32_t dtype;          /* FX_PRED_I8 .. FX_PRED_F64 */
+  int32_t reserved;
+} fx_pred_column;
+
+typedef struct fx_pred_op {
+  int32_t op;          /* FX_PRED_EQ .. FX_PRED_NOT */
+  int32_t column;      /* leaves: index into cols */
+  int64_t imm;         /* compares: the literal; FX_PRED_IS_NULL: nan_is_null */
+  int32_t set_offset;  /* FX_PRED_IS_IN: slice of set_pool */
+  int32_t set_length;
+} fx_pred_op;
+
+int fx_pred_limits(int* max_columns, int* max_ops, int* max_set, int* max_pool);
+int fx_pred_eval(const fx_pred_column* cols, int ncols, const fx_pred_op* ops, int nops,
+                 const int64_t* set_pool, int64_t n, int64_t row0, const uint32_t* and_mask,
+                 uint32_t* out_mask, uint64_t* out_count, void* stream);
 
 /* ------------------------------------------------------ corpus descriptor
  * The _ex entry points take the corpus as a descriptor, which also carries
