@@ -76,6 +76,8 @@ SYMBOLS = (
     "fx_code_probe_workspace_bytes",
     "fx_code_probe",
     "fx_code_mask",
+    "fx_code_qmask_workspace_bytes",
+    "fx_code_qmask",
     "fx_knn_search_rows_workspace_bytes",
     "fx_knn_search_rows",
     "fx_mask_compact_workspace_bytes",
@@ -255,6 +257,10 @@ def load() -> ctypes.CDLL:
         L.fx_code_probe.restype = ci
         L.fx_code_mask.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp]
         L.fx_code_mask.restype = ci
+        L.fx_code_qmask_workspace_bytes.argtypes = [i64, i64, psz]
+        L.fx_code_qmask_workspace_bytes.restype = ci
+        L.fx_code_qmask.argtypes = [vp, i64, vp, i64, i64, i64, vp, vp, sz, vp, i64, vp, vp, vp]
+        L.fx_code_qmask.restype = ci
         L.fx_knn_search_rows_workspace_bytes.argtypes = [i64, i64, ci, i64, i64, psz]
         L.fx_knn_search_rows_workspace_bytes.restype = ci
         L.fx_knn_search_rows.argtypes = [vp, ci, i64, i64, i64, vp, i64, vp, i64, ci, i64, vp, sz,
@@ -438,6 +444,10 @@ def kmeans_workspace_bytes(nb: int, bs: int, d: int, ks: int) -> int:
 
 def code_probe_workspace_bytes(nq: int, nb: int, ks: int) -> int:
     return _ws(load().fx_code_probe_workspace_bytes, nq, nb, ks)
+
+
+def code_qmask_workspace_bytes(nq: int, ncodes: int) -> int:
+    return _ws(load().fx_code_qmask_workspace_bytes, nq, ncodes)
 
 
 def search_rows_workspace_bytes(nrows: int, d: int, dtype: int, nq: int, k: int) -> int:

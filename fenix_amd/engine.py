@@ -603,12 +603,28 @@ class Engine:
             )
         )
 
-    def _qmask_tensors(self, shard: Shard, qmasks: torch.Tensor, shared: Optional[torch.Tensor],
+    def _qmask_tensors(self, shard: Shard, qmasks, shared: Optional[torch.Tensor],
                        packed: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """The per-query bitmaps [nq, words] as the library reads them (32-bit
         words, contiguous, the shared ``mask`` ANDed in) and, when ``packed``,
-        their bit matrix [n, fx_qmask_words(nq)] (fx_qmask_pack); caller holds lock."""
+        their bit matrix [n, fx_qmask_words(nq)] (fx_qmask_pack); caller holds lock.
+        ``qmasks`` may be the pair (bitmaps, packed) of ``code_qmask``, whose
+        shared mask is folded in already: both are used as they are."""
         words = (shard.n + 31) // 32
+        if isinstance(qmasks, (tuple, list)):
+            # (bitmaps, packed) of Engine.code_qmask: the shared mask is folded
+            # in and the bit matrix built already: no clone, no AND, no pack
+            qm, pk = qmasks
+            qw = _lib.qmask_words(qm.shape[0])
+            if (qm.dtype != torch.int32 or qm.dim() != 2 or qm.shape[1] < words
+                    or qm.device != self.device or not qm.is_contiguous()):
+                raise ValueError(f"qmasks pair: bitmaps must be contiguous int32 [nq, >= {words}] "
+                                 f"on {self.device}, got {tuple(qm.shape)}")
+            if (pk.dtype != torch.int32 or tuple(pk.shape) != (shard.n, qw)
+                    or pk.device != self.device or not pk.is_contiguous()):
+                raise ValueError(f"qmasks pair: packed must be contiguous int32 [{shard.n}, {qw}] "
+                                 f"on {self.device}, got {tuple(pk.shape)}")
+            return qm, pk if packed else None
         qm = qmasks
         if qm.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
             raise TypeError("qmasks must hold 32-bit words")
@@ -634,10 +650,12 @@ class Engine:
         """fx_knn_search_qmask_ex on one shard: query i searches the rows its own
         bitmap ``qmasks[i]`` admits (AND ``shared``), all of them in one pass
         over the int8 filter image where the library plans the filter; caller
-        holds lock."""
+        holds lock.  ``qmasks``: a [nq, words] tensor, or the pair (bitmaps,
+        packed) of ``code_qmask`` (``shared`` is then folded in already)."""
         nq = queries.shape[0]
-        if qmasks.shape[0] != nq:
-            raise ValueError(f"qmasks holds {qmasks.shape[0]} bitmaps for {nq} queries")
+        have = (qmasks[0] if isinstance(qmasks, (tuple, list)) else qmasks).shape[0]
+        if have != nq:
+            raise ValueError(f"qmasks holds {have} bitmaps for {nq} queries")
         img, info, _ = self.filter_image(shard, nq, k, metric, qmask=True)
         qm, pk = self._qmask_tensors(shard, qmasks, shared, img is not None)
         c = shard.corpus()
@@ -917,7 +935,10 @@ class Engine:
         this device, query i's own row bitmap of the shard (``masks[i]`` is
         ANDed into each; ``counts[i]``, then the per-query kept rows, is not
         needed): every query searches its own rows in one call
-        (fx_knn_search_qmask_ex), results equal to nq masked searches."""
+        (fx_knn_search_qmask_ex), results equal to nq masked searches.  A
+        shard's entry may also be the pair (bitmaps, packed) of ``code_qmask``,
+        whose shared mask is folded in already (``masks[i]`` is not applied
+        again, nothing is cloned or packed)."""
         queries = _to_device(queries, self.device)
         nq = queries.shape[0]
         mask_of = (lambda i: masks[i]) if masks else (lambda i: None)
@@ -1089,6 +1110,28 @@ class Engine:
                 _ptr(row_code), n, _ptr(sel), ncodes, _ptr(filter), _ptr(out), _ptr(cnt),
                 self._stream()))
         return out, cnt
+
+    def code_qmask(self, row_code: torch.Tensor, sel: torch.Tensor, ncodes: int,
+                   filter: Optional[torch.Tensor] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """fx_code_qmask: the masks of a batch of probe searches in one pass over
+        the row codes.  sel [nq, >= ceil(ncodes / 32)] int32 (code_probe's
+        bitmaps) -> (bitmaps [nq, ceil(n / 32)] int32, packed [n,
+        fx_qmask_words(nq)] int32, kept-row counts [nq] int64), ``filter``
+        folded into all three.  Raises NotImplementedError (FX_EUNSUPPORTED)
+        where the code-major table would be too large."""
+        n, nq = row_code.shape[0], sel.shape[0]
+        sel = sel.view(torch.int32).contiguous()
+        out = torch.empty((nq, max(1, (n + 31) // 32)), dtype=torch.int32, device=self.device)
+        pk = torch.empty((n, _lib.qmask_words(nq)), dtype=torch.int32, device=self.device)
+        cnt = torch.empty(nq, dtype=torch.int64, device=self.device)
+        nbytes = _lib.code_qmask_workspace_bytes(nq, ncodes)
+        with self.lock:
+            ws = self._workspace(nbytes)
+            _lib.check(_lib.load().fx_code_qmask(
+                _ptr(row_code), n, _ptr(sel), sel.shape[1], nq, ncodes, _ptr(filter), _ptr(ws),
+                ws.numel(), _ptr(out), out.shape[1], _ptr(pk), _ptr(cnt), self._stream()))
+        return out, pk, cnt
 
     def pred_eval(self, program, columns: Sequence["PredColumn"], n: int, row0: int,
                   and_mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -1287,6 +1330,15 @@ def _np_dtype(dt: torch.dtype):
     return {torch.float32: np.float32, torch.float16: np.float16, torch.uint8: np.uint8}[dt]
 
 
+# From this many probe targets on, io.index.call_many builds their masks in one
+# pass over the codes (Engine.code_qmask) instead of one fx_code_mask per
+# target: the smallest batch, because the one pass won at every measured size
+# (profiles/search_many.json, tools/search_many_sweep.py: 10M rows, 65 536
+# codes, with and without a shared filter: 0.08-0.09 against 0.25 ms for 2
+# targets, 0.10 against 0.87 for 16, 0.56 against 11.8 for 256)
+CODE_QMASK_MIN_NQ = 2
+
+
 def qmask_batch_pays(counts: Sequence[Optional[int]], n: int, d: int, itemsize: int, nq: int,
                      min_ratio: Optional[float] = None) -> bool:
     """Whether ``nq`` concurrent searches of an n x d column, request q keeping
@@ -1338,6 +1390,7 @@ def _batch_qmasks(shards: Sequence[Shard], extras: Sequence[Optional[tuple]]):
 def search_host(shards: Sequence[Shard], queries: torch.Tensor, metric: int, k: int,
                 masks: Optional[Sequence[Optional[torch.Tensor]]] = None,
                 counts: Optional[Sequence[Optional[int]]] = None, gather: bool = False,
+                qmasks: Optional[Sequence] = None,
                 ) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
     """``search_all`` with the results on the host — what io.index.call
     needs: (dist [nq, k] f32, rows [nq, k] i64, vectors [nq, k, D] or None).
@@ -1350,7 +1403,10 @@ def search_host(shards: Sequence[Shard], queries: torch.Tensor, metric: int, k: 
     concurrent requests over the same shards run as one batch, and a batch
     in which any request brings masks runs as one per-query-mask search
     where ``qmask_batch_pays`` says so (every shard served by the int8
-    filter), else request by request exactly as each would run alone."""
+    filter), else request by request exactly as each would run alone.
+    ``qmasks`` (io.index.call_many's probe batches): per shard the caller's own
+    per-query masks, as ``Engine.search`` takes them; the batch then runs as
+    one per-query-mask search, never through the coalescer."""
     def run(qs: torch.Tensor, kk: int, ms=None, cs=None, qms=None) -> Tuple[np.ndarray, ...]:
         if gather and len(shards) == 1 and shards[0].n > 0:
             return _search_packed(shards[0], qs, metric, kk, ms, cs, qms)
@@ -1381,7 +1437,9 @@ def search_host(shards: Sequence[Shard], queries: torch.Tensor, metric: int, k: 
             outs.append(run(torch.from_numpy(qs[i:i + 1]), kk, ms, cs))
         return tuple(np.concatenate(p) for p in zip(*outs))
 
-    if queries.shape[0] == 1 and coalesce.enabled() and k <= _lib.load().fx_max_k():
+    if qmasks is not None:
+        parts = run(queries, k, masks, counts, qmasks)
+    elif queries.shape[0] == 1 and coalesce.enabled() and k <= _lib.load().fx_max_k():
         key = (tuple((id(s.data), s.data.data_ptr(), s.n, s.row_base) for s in shards), metric,
                gather)
         extra = None if masks is None and counts is None else (masks, counts)

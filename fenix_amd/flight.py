@@ -13,8 +13,14 @@ Mirrors src/fenix/flight.py of the reference:
 
 The wire format (descriptor dict, ``target`` column, result schema, action
 names and their pickled bodies) is unchanged, so a reference client can talk
-to this server and vice versa.  Only ``search`` / ``do_exchange`` / ``do_put``
-are on the accelerated path; the admin surface is kept for drop-in use and
+to this server and vice versa.  One extension the reference server does not
+understand: ``Flight.search_many`` sends the same descriptor dict plus the key
+``"many": True`` and nq targets as the rows of the ``target`` column;
+``do_exchange`` pops the key and answers with ``io.index.call_many`` (a
+descriptor without it takes the reference's path untouched; the reference
+server would pass ``many`` to ``index.call`` and fail with a TypeError).
+Only ``search`` / ``search_many`` / ``do_exchange`` / ``do_put`` are on the
+accelerated path; the admin surface is kept for drop-in use and
 written here as tables: server actions dispatch through ``Server._ACTIONS``,
 the read options that ``read_table`` sets before a ``do_get`` live in one
 locked dict (``Server._read_opts``, not attributes of the server object), and
@@ -102,10 +108,15 @@ class Server(fl.FlightServerBase):
         writer: fl.MetadataRecordBatchWriter,
     ) -> None:
         config = pickle.loads(descriptor.command)
+        many = config.pop("many", False)
         config["target"] = reader.read_all().column("target").combine_chunks()
         config["filter"] = pickle.loads(config["filter"])
 
-        data = io.index.call(self.root, **config)
+        if many:  # Flight.search_many: the rows of the target column are nq targets
+            config["targets"] = config.pop("target")
+            data = io.index.call_many(self.root, **config)
+        else:
+            data = io.index.call(self.root, **config)
 
         writer.begin(data.schema)
         writer.write_table(data)
@@ -143,6 +154,32 @@ class Server(fl.FlightServerBase):
 
 # the metric names Flight.search accepts (coder.py:38-50 and their aliases)
 METRICS = frozenset({"cosine", "dot", "inner_product", "l2", "euclidean"})
+
+
+def search_command(coding, source, column, metric, select, filter, maxval, probes,
+                   many: bool = False) -> dict:
+    """The descriptor dict of a search (flight.py:262-271 of the reference, the
+    filter pickled on its own).  ``many`` adds the key ``"many": True`` of
+    ``Flight.search_many``; without it the dict is the reference's, key for key."""
+    command = {"coding": coding, "source": source, "column": column, "metric": metric,
+               "select": select, "filter": pickle.dumps(filter), "maxval": maxval,
+               "probes": probes}
+    if many:
+        command["many"] = True
+    return command
+
+
+def target_rows(targets) -> "pa.Array | pa.ChunkedArray":
+    """The ``target`` column of ``Flight.search_many``: one list per target (a
+    2-D ndarray or Tensor becomes a FixedSizeListArray of its rows)."""
+    if type(targets).__module__.split(".")[0] == "torch":  # Tensor, without importing torch
+        targets = targets.numpy()
+    if isinstance(targets, np.ndarray):
+        if targets.ndim != 2:
+            raise ValueError(f"targets must be 2-D (one row per target), got {targets.ndim}-D")
+        flat = pa.array(np.ascontiguousarray(targets).ravel())
+        return pa.FixedSizeListArray.from_arrays(flat, targets.shape[1])
+    return targets
 
 
 @dataclass(frozen=True)
@@ -222,15 +259,36 @@ class Flight:
         assert, descriptor dict (filter pickled twice) and ``target`` table."""
         assert metric in METRICS
 
-        command = {"coding": coding, "source": source, "column": column, "metric": metric,
-                   "select": select, "filter": pickle.dumps(filter), "maxval": maxval,
-                   "probes": probes}
+        command = search_command(coding, source, column, metric, select, filter, maxval, probes)
         if type(target).__module__.split(".")[0] == "torch":  # Tensor, without importing torch
             target = target.numpy()
         if isinstance(target, np.ndarray):
             target = pa.array(target)
-        table = pa.table({"target": target})
+        return self._exchange(command, pa.table({"target": target}))
 
+    def search_many(
+        self,
+        targets,  # FixedSizeListArray | ChunkedArray of nq rows | 2-D ndarray | Tensor
+        source: str | Sequence[str],
+        column: str,
+        metric: str,
+        coding: str | None = None,
+        select: Sequence[str] | None = None,
+        filter: pc.Expression | None = None,
+        maxval: int | None = None,
+        probes: int | None = None,
+    ) -> pa.Table:
+        """nq searches in one round trip (``io.index.call_many``; an extension,
+        not understood by the reference server): ``search``'s descriptor plus
+        ``"many": True``, the targets as the rows of the ``target`` column.  The
+        result carries ``__TARGET__``, the position of each row's target."""
+        assert metric in METRICS
+
+        command = search_command(coding, source, column, metric, select, filter, maxval, probes,
+                                 many=True)
+        return self._exchange(command, pa.table({"target": target_rows(targets)}))
+
+    def _exchange(self, command: dict, table: pa.Table) -> pa.Table:
         writer, reader = self.conn.do_exchange(
             fl.FlightDescriptor.for_command(pickle.dumps(command)))
         with writer:

@@ -35,6 +35,12 @@ behaviour:
 * the result is one chunk (``combine_chunks``, index.py:170); ``__DISTANCE__``
   has the column's value type (the UDF's output type, index.py:153-159).
 
+``call_many(root, coding, source, column, targets, ...)`` (an extension, no
+counterpart in the reference): ``call`` for nq targets in one request, the
+result carrying ``__TARGET__``.  One filter evaluation, one batched search;
+with ``probes`` the per-target row masks come from one pass over the code
+column (fx_code_qmask) and feed one per-query-mask search.
+
 ``make`` / ``load`` / ``list`` / ``drop`` (index.py:19-78): index files
 ``<root>/indexes/<source>/<column>/<name>.arrow`` holding one int64
 ``__CODED_ID__`` per row, written in the source's batch layout; ``make``
@@ -486,6 +492,41 @@ def _probe_masks(code: coder.Coding, q: np.ndarray, probes: int, shard_info, cod
     return out, counts, n_rows, host
 
 
+def _open_sources(root: str, coding: str | None, source, column: str):
+    """The table ``call`` searches: -> (data, parts, version, code_parts).
+    Named sources come from the resident cache; with ``coding`` each is joined
+    with its ``__CODED_ID__`` column (``load``)."""
+    if isinstance(source, pa.Table):
+        return source, [(None, source)], None, None
+    names = [source] if isinstance(source, str) else [*source]
+    data, parts, version = _resident.sources(root, names)
+    code_parts = None
+    if coding is not None:
+        coder.load(root, coding)
+        code_parts = [_resident.load_table(_index_path(root, coding, s, column))
+                      for s in names]
+        data = table.join(*[table.join(t, it, axis=1)
+                            for (_, t), (_, it) in zip(parts, code_parts)])
+        version = version + tuple(k for k, _ in code_parts)
+    return data, parts, version, code_parts
+
+
+def _shared_filter(data: pa.Table, parts, version, filter, shard_info, want_counts: bool):
+    """The row predicate of index.py:161, evaluated once: by the device program
+    where ``predicate`` compiles it, else by pyarrow.  -> (program or None, host
+    bool mask or None, per-shard device bitmaps or None, per-shard kept rows of
+    a device evaluation when ``want_counts`` else None)."""
+    program = _device_filter(data, parts, filter) if filter is not None else None
+    fmask = _filter_mask(data, filter) if filter is not None and program is None else None
+    masks, counts = None, None
+    if program is not None:
+        masks, counts = _device_masks(program, shard_info, parts, version, want_counts)
+    if fmask is not None:
+        masks = [_engine.device_mask(fmask[s.row_base : s.row_base + s.n], s.data.device)
+                 for s, _, _ in shard_info]
+    return program, fmask, masks, counts
+
+
 def call(
     root: str,
     coding: str | None,
@@ -498,19 +539,7 @@ def call(
     maxval: int | None = None,
     probes: int | None = None,
 ) -> pa.Table:
-    code_parts = None
-    if isinstance(source, pa.Table):
-        data, parts, version = source, [(None, source)], None
-    else:
-        names = [source] if isinstance(source, str) else [*source]
-        data, parts, version = _resident.sources(root, names)
-        if coding is not None:
-            coder.load(root, coding)
-            code_parts = [_resident.load_table(_index_path(root, coding, s, column))
-                          for s in names]
-            data = table.join(*[table.join(t, it, axis=1)
-                                for (_, t), (_, it) in zip(parts, code_parts)])
-            version = version + tuple(k for k, _ in code_parts)
+    data, parts, version, code_parts = _open_sources(root, coding, source, column)
 
     type = data.schema.field(column).type
     q = _target_values(target, type)
@@ -530,16 +559,10 @@ def call(
     m = coder.metric_id(metric)
     _engine.value_dtype(type)
 
-    program = _device_filter(data, parts, filter) if filter is not None else None
-    fmask = _filter_mask(data, filter) if filter is not None and program is None else None
     shard_info = _resident.shards(parts, column, _engine.devices())
     shards = [s for s, _, _ in shard_info]
-    masks = None
-    if program is not None:
-        masks, counts = _device_masks(program, shard_info, parts, version, code is None)
-    if fmask is not None:
-        masks = [_engine.device_mask(fmask[s.row_base : s.row_base + s.n], s.data.device)
-                 for s in shards]
+    program, fmask, masks, counts = _shared_filter(data, parts, version, filter, shard_info,
+                                                   code is None)
     if code is not None:
         if code_parts is None:
             raise ValueError("a probe search needs named sources with an index")
@@ -581,3 +604,256 @@ def call(
     dt = _dist_type(type)
     out = out.append_column(DIST_COL, pa.array(dist.astype(dt.to_pandas_dtype()), type=dt))
     return out.select(select).combine_chunks()
+
+
+# ------------------------------------------------------------ many targets --
+TARGET_COL: str = "__TARGET__"
+# targets per engine call: the largest batch this project has measured (README);
+# nothing bounds the workspace of a larger batch at large k
+MANY_CHUNK: int = 256
+
+
+def _targets_values(targets, type: pa.DataType) -> np.ndarray:
+    """``_target_values`` for the nq >= 1 rows of ``targets`` -> [nq, D] f32.
+
+    targets: a FixedSizeListArray / ListArray / ChunkedArray of nq rows, or a
+    2-D ndarray / Tensor (quint8 columns: nq float rows of prod(shape) values).
+    Each row is normalised and cast as ``_target_values`` does one target (the
+    f16 cast, ``ArrowInvalid`` for a wrong length); rows that already have the
+    column's value type and length are copied in one piece, which is the same
+    thing."""
+    if isinstance(targets, pa.ChunkedArray):
+        targets = targets.combine_chunks()
+    if isinstance(targets, Tensor):
+        targets = targets.numpy()
+    d = _engine.list_size(type)
+    quint8 = isinstance(type, pa.ExtensionType)
+    if isinstance(targets, np.ndarray):
+        if targets.ndim != 2:
+            raise ValueError(f"targets must be 2-D (one row per target), got {targets.ndim}-D")
+        rows = [targets[i] for i in range(targets.shape[0])]
+        if targets.shape[1] == d:
+            if quint8:
+                rows, out = None, np.array(targets, dtype=np.float32)
+            elif pa.types.is_float16(type.value_type):
+                rows, out = None, targets.astype(np.float16).astype(np.float32)
+            elif targets.dtype == np.float32 and pa.types.is_float32(type.value_type):
+                rows, out = None, np.array(targets, dtype=np.float32)
+    elif isinstance(targets, pa.Array):
+        if not (pa.types.is_fixed_size_list(targets.type) or pa.types.is_list(targets.type)
+                or pa.types.is_large_list(targets.type)):
+            raise TypeError(f"targets must hold one list per target, got {targets.type}")
+        rows = [targets[i] for i in range(len(targets))]
+        if (pa.types.is_fixed_size_list(targets.type) and targets.type.list_size == d
+                and targets.null_count == 0 and targets.flatten().null_count == 0
+                and (quint8 or targets.type == type)):
+            flat = targets.flatten().to_numpy(zero_copy_only=False)
+            rows, out = None, np.array(flat, dtype=np.float32).reshape(len(targets), d)
+    else:
+        raise TypeError(f"unsupported targets type {_type_name(targets)}")
+    if rows is not None:
+        if not rows:
+            raise ValueError("targets holds no row")
+        rows = [r.values.to_numpy(zero_copy_only=False) if isinstance(
+            r, (pa.ListScalar, pa.LargeListScalar)) else r for r in rows]
+        out = np.concatenate([_target_values(r, type) for r in rows])
+    if out.shape[0] < 1:
+        raise ValueError("targets holds no row")
+    return np.ascontiguousarray(out, dtype=np.float32)
+
+
+def _type_name(x) -> str:
+    return f"{x.__class__.__module__}.{x.__class__.__qualname__}"
+
+
+def _flatten_many(dist: np.ndarray, rows: np.ndarray):
+    """[nq, k] results -> their valid slots (row >= 0; the NaN / -1 padding of
+    a target with fewer than k admitted rows is dropped), target 0's first,
+    each target's in the search's (distance, row) order.
+    -> (dist, rows, target position int32, keep [nq, k] bool)."""
+    keep = rows >= 0
+    tidx = np.broadcast_to(np.arange(rows.shape[0], dtype=np.int32)[:, None], rows.shape)[keep]
+    return dist[keep], rows[keep], np.ascontiguousarray(tidx), keep
+
+
+def _many_table(out: pa.Table, dist: np.ndarray, tidx: np.ndarray, type: pa.DataType,
+                select: Sequence[str]) -> pa.Table:
+    """The taken columns of every target's rows plus ``__DISTANCE__`` (the
+    column's value type) and ``__TARGET__`` (int32), in ``select`` order."""
+    dt = _dist_type(type)
+    out = out.append_column(DIST_COL, pa.array(dist.astype(dt.to_pandas_dtype()), type=dt))
+    out = out.append_column(TARGET_COL, pa.array(tidx, type=pa.int32()))
+    return out.select([*select]).combine_chunks()
+
+
+def _probe_sel(code: coder.Coding, q: np.ndarray, probes: int, dev0) -> torch.Tensor:
+    """One Engine.distances of all targets against the codewords and one
+    fx_code_probe -> their selected-code bitmaps [nq, words] on ``dev0``."""
+    nb = int(code["config"]["num_codebooks"])
+    ks = int(code["config"]["codebook_size"])
+    with torch.cuda.device(dev0):
+        eng0 = _engine.Engine.get(dev0)
+        cw = code["tensor"].to(dev0, torch.float32).contiguous()
+        d = eng0.distances(_engine.Shard(cw.reshape(nb * ks, -1), 0), torch.from_numpy(q).to(dev0),
+                           coder.metric_id(code["config"]["metric"]))
+        _, _, sel = eng0.code_probe(d.reshape(q.shape[0], nb, ks), int(probes), sel=True)
+    return sel
+
+
+def _probe_qmasks(sel: torch.Tensor, ncodes: int, shard_info, code_parts, masks):
+    """Per shard one Engine.code_qmask over its slice of the resident code
+    column, the shared filter folded in; one D2H of the counts per device.
+    -> (per-shard (bitmaps, packed), kept rows int64 [shards, nq])."""
+    pairs, cnts = [], []
+    for i, (s, src, start) in enumerate(shard_info):
+        dev = s.data.device
+        with torch.cuda.device(dev):
+            key, t = code_parts[src]
+            rc = _resident.code_column(key, t, CODE_COL, dev)[start : start + s.n]
+            bm, pk, cnt = _engine.Engine.get(dev).code_qmask(
+                rc, sel.to(dev), ncodes, masks[i] if masks is not None else None)
+        pairs.append((bm, pk))
+        cnts.append(cnt)
+    counts = np.zeros((len(cnts), sel.shape[0]), dtype=np.int64)
+    by_dev = {}
+    for i, c in enumerate(cnts):
+        by_dev.setdefault(c.device, []).append(i)
+    for dev, idx in by_dev.items():
+        with torch.cuda.device(dev):
+            counts[idx] = torch.stack([cnts[i] for i in idx]).cpu().numpy()
+    return pairs, counts
+
+
+def _many_probe_chunk(code, q, probes, shard_info, code_parts, masks, m, k, gather):
+    """One chunk of a probe search of many targets: the masks of all of them
+    from one pass over the codes, then one per-query-mask search where
+    ``qmask_batch_pays`` (as for coalesced batches), else target by target with
+    its bitmap row and count (selective probe sets keep the row-list scan)."""
+    shards = [s for s, _, _ in shard_info]
+    nq = q.shape[0]
+    nb = int(code["config"]["num_codebooks"])
+    ks = int(code["config"]["codebook_size"])
+    dev0 = shards[0].data.device
+    if nq >= _engine.CODE_QMASK_MIN_NQ:
+        try:
+            sel = _probe_sel(code, q, probes, dev0)
+            pairs, counts = _probe_qmasks(sel, ks**nb, shard_info, code_parts, masks)
+        except NotImplementedError:  # FX_EUNSUPPORTED: the per-target masks
+            pairs = None
+    else:
+        pairs = None
+    if pairs is None:
+        outs = []
+        for j in range(nq):
+            ms, cs, _, _ = _probe_masks(code, q[j : j + 1], probes, shard_info, code_parts, masks)
+            outs.append(_engine.search_host(shards, torch.from_numpy(q[j : j + 1]), m, k, ms, cs,
+                                            gather=gather))
+        return outs
+    served = k <= _lib.max_k() and all(
+        s.n > 0 and _lib.get_option("filter_image") == 8
+        and _lib.qmask_filter_used(s.n, s.d, s.dtype_id, nq, k, m) != 0 for s in shards)
+    totals = [int(c) for c in counts.sum(axis=0)]
+    if served and _engine.qmask_batch_pays(totals, sum(s.n for s in shards), shards[0].d,
+                                           shards[0].data.element_size(), nq):
+        return [_engine.search_host(shards, torch.from_numpy(q), m, k, gather=gather,
+                                    qmasks=pairs)]
+    outs = []
+    for j in range(nq):
+        ms = [bm[j].clone() for bm, _ in pairs]
+        cs = [int(counts[i, j]) for i in range(len(pairs))]
+        outs.append(_engine.search_host(shards, torch.from_numpy(q[j : j + 1]), m, k, ms, cs,
+                                        gather=gather))
+    return outs
+
+
+def call_many(
+    root: str,
+    coding: str | None,
+    source: str | Sequence[str] | pa.Table,
+    column: str,
+    targets: pa.Array | pa.ChunkedArray | np.ndarray | Tensor,
+    metric: str | None = None,
+    select: Sequence[str] | None = None,
+    filter: pc.Expression | None = None,
+    maxval: int | None = None,
+    probes: int | None = None,
+) -> pa.Table:
+    """``call`` for nq >= 1 targets in one request (an extension: the reference
+    has no such entry point).  The result holds the ``select`` columns, then
+    ``__DISTANCE__``, then ``__TARGET__`` (int32, the target's position):
+    target 0's rows first, each target's ascending by (distance, row).  For
+    every i the rows with ``__TARGET__ == i`` are those of ``call(...,
+    target=targets[i], ...)``: the same rows, order, distance bits and column
+    values whenever that call keeps more than ``maxval`` rows, else the same
+    rows sorted by (distance, row) (``call`` returns table order there).
+    ``maxval`` is required.
+
+    The filter is evaluated once.  Without probes all targets run as one
+    batched search under the shared mask; with probes their masks come from
+    one pass over the code column (fx_code_qmask) and the batch runs as one
+    per-query-mask search where that pays, else target by target.  Targets are
+    processed ``MANY_CHUNK`` at a time."""
+    if maxval is None or int(maxval) < 1:
+        raise ValueError("call_many: maxval is required (>= 1)")
+    data, parts, version, code_parts = _open_sources(root, coding, source, column)
+
+    type = data.schema.field(column).type
+    q = _targets_values(targets, type)
+
+    code = None
+    if coding is not None and probes is not None:
+        code = coder.load(root, coding)
+
+        if metric is None:
+            metric = code["config"]["metric"]
+
+    select = [*select] if select is not None else data.column_names
+    select = select + [DIST_COL, TARGET_COL]
+
+    assert metric is not None
+
+    m = coder.metric_id(metric)
+    _engine.value_dtype(type)
+    k = int(maxval)
+
+    shard_info = _resident.shards(parts, column, _engine.devices())
+    shards = [s for s, _, _ in shard_info]
+    _, fmask, masks, counts = _shared_filter(data, parts, version, filter, shard_info,
+                                             code is None)
+    if code is not None:
+        if code_parts is None:
+            raise ValueError("a probe search needs named sources with an index")
+        nb = int(code["config"]["num_codebooks"])
+        ks = int(code["config"]["codebook_size"])
+        if probes > ks**nb:
+            raise RuntimeError("selected index k out of range")  # torch.topk in coder.call
+    elif fmask is not None:
+        counts = [int(fmask[s.row_base : s.row_base + s.n].sum()) for s in shards]
+
+    base_cols = [c for c in dict.fromkeys(select) if c not in (DIST_COL, TARGET_COL)]
+    gather = column in base_cols
+    outs = []
+    if data.num_rows > 0 and shards:
+        for lo in range(0, q.shape[0], MANY_CHUNK):
+            qc = q[lo : lo + MANY_CHUNK]
+            if code is not None:
+                outs += _many_probe_chunk(code, qc, probes, shard_info, code_parts, masks, m, k,
+                                          gather)
+            elif k > _lib.max_k():  # beyond the fused scan's k: target by target
+                outs += [_engine.search_host(shards, torch.from_numpy(qc[j : j + 1]), m, k, masks,
+                                             counts, gather=gather) for j in range(qc.shape[0])]
+            else:
+                outs.append(_engine.search_host(shards, torch.from_numpy(qc), m, k, masks, counts,
+                                                gather=gather))
+    if outs:
+        dist = np.concatenate([o[0] for o in outs])
+        rows = np.concatenate([o[1] for o in outs])
+        vecs = np.concatenate([o[2] for o in outs]) if all(o[2] is not None for o in outs) else None
+    else:
+        dist = np.zeros((q.shape[0], 0), dtype=np.float32)
+        rows = np.zeros((q.shape[0], 0), dtype=np.int64)
+        vecs = None
+    dist, rows, tidx, keep = _flatten_many(dist, rows)
+    vecs = vecs[keep] if vecs is not None else None
+    out = _take_columns(data, base_cols, rows, column, shards, version, vecs)
+    return _many_table(out, dist, tidx, type, select)

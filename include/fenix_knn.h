@@ -673,6 +673,35 @@ int fx_code_assign_ex(const fx_corpus* c, const float* codewords, int64_t nb, in
 int fx_kmeans_step_ex(const fx_corpus* sample, int64_t nb, float* codewords, int64_t ks,
                       int metric, void* ws, size_t ws_bytes, void* stream);
 
+/*
+ * The row masks of a batch of probe searches in one pass over the codes (added
+ * within 1.4; fx_version() is still 104): index.py:113-126 for nq targets at
+ * once.  sel [nq][sel_stride] is fx_code_probe's out_sel (sel_stride >=
+ * ceil(ncodes / 32)), filter the optional shared row bitmap of fx_code_mask.
+ * Outputs, each nullable, at least one given:
+ *   out_masks [nq][mask_stride] (mask_stride >= ceil(n / 32)): row q is, bit
+ *     for bit, what fx_code_mask(row_code, n, sel + q * sel_stride, ncodes,
+ *     filter, ...) writes; bits of rows >= n in the last word are zero, words
+ *     past ceil(n / 32) are not written;
+ *   out_qmask [n][fx_qmask_words(nq)], 16-B aligned: fx_qmask_pack of
+ *     out_masks (padding bits zero, rows >= n not written);
+ *   out_counts [nq] uint64 on the device: the rows kept per target.
+ * A code outside [0, ncodes) admits its row for no target.  sel is transposed
+ * into a code-major table in ws (ncodes x fx_qmask_words(nq) words, read from
+ * L2); row_code and filter are then read once per group of 128 targets, and
+ * nothing of size nq * n is read.  Asynchronous, no host synchronisation.
+ * FX_EINVAL before any launch: a null row_code (n > 0), sel or ws, nq < 1,
+ * ncodes < 1, n < 0, a short sel_stride or mask_stride, a short workspace, no
+ * output, out_qmask or ws not 16-B aligned.  n == 0: the counts are zeroed.
+ * FX_EUNSUPPORTED: a table above 1 GiB or more than 65 535 target groups (the
+ * caller then masks target by target, fx_code_mask).
+ */
+int fx_code_qmask_workspace_bytes(int64_t nq, int64_t ncodes, size_t* out_bytes);
+int fx_code_qmask(const int64_t* row_code, int64_t n, const uint32_t* sel, int64_t sel_stride,
+                  int64_t nq, int64_t ncodes, const uint32_t* filter, void* ws, size_t ws_bytes,
+                  uint32_t* out_masks, int64_t mask_stride, uint32_t* out_qmask,
+                  uint64_t* out_counts, void* stream);
+
 /* ------------------------------------------------------ multi-GPU exchange
  * Single-process communicator over RCCL (xGMI): one rank per listed device
  * (a serving process driving every GPU of a node).  fx_allgather_topk gathers
